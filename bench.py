@@ -30,11 +30,11 @@ T_PROCESS_START = time.perf_counter()        # the wall-clock budget (--budget-s
 # dmabuf IPC (the only kind this pool's driver supports) must be selected BEFORE anything initialises HSA: torch.cuda.set_device()
 # below already does, so this cannot wait until the process group is created (VERDICT r2 / ADVICE r2)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# HIP maps streams onto a few hardware queues (4 by default) and two streams that share a queue run one after the other.  Measured
-# on MI355X (profiles/r03_overlap_env.txt): with the defaults the stream torch's RCCL process group communicates on lands on the
-# SAME queue as the default stream -- the per-chunk asynchronous all-gather then ran 0 % under the compute kernels; with more
-# hardware queues, or a high-priority communication stream, 85 %.  Both must be in the environment before the runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# HIP maps streams onto a few hardware queues and two streams that share a queue run one after the other.  Measured on MI355X
+# (profiles/r03_overlap_env.txt): with the defaults the stream torch's RCCL process group communicates on lands on the SAME queue as
+# the default stream -- the per-chunk asynchronous all-gather then ran 0 % under the compute kernels; with a high-priority
+# communication stream, 85 %.  It must be in the environment before the runtime starts.  The number of hardware queues is left to
+# the machine's own setting: they are a slot pool shared by every process on the card.
 os.environ.setdefault("TORCH_NCCL_HIGH_PRIORITY", "1")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -153,7 +153,65 @@ def parse(argv=None):
     ap.add_argument("--inject-failure", default=None, metavar="LEG",
                     help="test hook: raise inside the optional leg LEG (column_sharing | bf16x3 | bf16x3_column_sharing | bf16x3_attention | "
                          "bf16x6) to prove that no optional leg can cost the headline line")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; index files float64), "
+                         "at most 64 MB in all: an output that does not fit is written as a fixed, seeded sample (see dump_outputs)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _rows_of(blocks, idx):
+    """Rows `idx` (sorted indices into the concatenation of the row blocks) as one host array (len(idx), width)."""
+    out, base = [], 0
+    for b in blocks:
+        n = b.shape[0]
+        lo, hi = np.searchsorted(idx, [base, base + n])
+        if hi > lo:
+            out.append(b.reshape(n, -1).index_select(0, _index_tensor(idx[lo:hi] - base, b.device)).cpu().numpy())
+        base += n
+    return np.concatenate(out)
+
+
+def _index_tensor(idx, device):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(device)
+
+
+def dump_outputs(out_dir, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write each output of the timed path's last step to `out_dir`, `limit` bytes in all.  `outputs` maps a name to a
+    list of device tensors (float32) whose first dimensions concatenate to the output's rows.  An output that fits its equal share of
+    the limit is written whole as <name>.npy (rows, width).  A larger one is written as a sample that is the same in every run with the
+    same arguments (seeded, sorted indices): <name>_cols.npy = every row at K columns, <name>_rows.npy = R whole rows, with the indices
+    in <name>_cols_index.npy / <name>_rows_index.npy (float64).  Returns {file name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = (limit - 64 * 1024) // max(1, len(outputs))              # 64 KB for the .npy headers
+    written = {}
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name + ".npy"] = list(arr.shape)
+    for name, blocks in outputs.items():
+        n = sum(int(b.shape[0]) for b in blocks)
+        width = int(np.prod(blocks[0].shape[1:]))
+        if n * width * 4 <= share:
+            save(name, _rows_of(blocks, np.arange(n)))
+            continue
+        rs = np.random.RandomState(0)
+        k = max(1, min(width, share // 2 // (4 * n + 8)))               # every row at k columns: at most half the share
+        cols = np.sort(rs.choice(width, k, replace=False))
+        r = max(1, min(n, (share - k * (4 * n + 8)) // (4 * width + 8)))
+        rows = np.sort(rs.choice(n, r, replace=False))
+        ct = _index_tensor(cols, blocks[0].device)
+        save(name + "_cols", np.concatenate([b.reshape(b.shape[0], -1).index_select(1, ct).cpu().numpy() for b in blocks]))
+        save(name + "_cols_index", cols.astype(np.float64))
+        save(name + "_rows", _rows_of(blocks, rows))
+        save(name + "_rows_index", rows.astype(np.float64))
+    return written
 
 
 def launcher_argv(n, argv, port, python=None):
@@ -755,6 +813,21 @@ def main():
     fe_ms = ev0.elapsed_time(ev1) / 5
     stages["frontend"] = fe_ms
 
+    # ---- --dump-outputs: what a caller of the timed path holds after its last step (the legs below overwrite these buffers).  With a
+    # gatherer, every rank's rows as they arrived on this rank; otherwise this rank's own rows.
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        holder = Mode.gatherer if Mode.gatherer is not None else Mode.direct
+        outputs = {}
+        if holder is not None:
+            outputs["coef" if Mode.kind == "coef" else a.head] = [v for r in range(world) for v in holder.rows(r)]
+        if holder is None or Mode.kind == "coef":
+            outputs[a.head] = [Mode.out]
+        if mesh is not None:
+            vgather = mesh[3]
+            outputs["verts"] = [v for r in range(world) for v in vgather.rows(r)] if vgather is not None else [mesh[2]]
+        dumped = dump_outputs(a.dump_outputs, outputs)
+
     n_chunks = (F + a.chunk - 1) // a.chunk
     # one GPU: the budget decides which optional legs run.  N > 1: optional legs run only with --all-legs, and then on EVERY rank or none
     # (a rank that skipped alone would leave its peers waiting in a collective), so the budget admits everything there
@@ -830,6 +903,8 @@ def main():
                             "frac_of_fp32_mfma_peak_by_flop": round(F * FLOP_ATTENTION_PER_FRAME / (att_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if att_ms > 0 else None,
                             "mfma_util_pct_counters": att_util, "mfma_util_pct_gemms_counters": att_gemms, "counters_source": att_src}
         res["peak_device_memory_gb"] = round(torch.cuda.max_memory_allocated(dev) / 1e9, 2)
+        if dumped is not None:
+            res["outputs_dumped"] = {"dir": a.dump_outputs, "files": dumped}
         res["wall_clock"] = dict(budget.report(), headline_at_s=round(budget.elapsed(), 1))
         emit(res, final=False)
 

@@ -182,3 +182,32 @@ def test_thread_scan_is_bounded():
     cost.update({8: 3.0, 16: 2.9, 32: 2.8})
     best, log = bench.thread_scan(probe, [8, 16, 32, 64], lambda n: now.update(nt=n), clock=lambda: now["t"], cap_s=5.0)
     assert calls == [8, 16] and best == 16                                                    # the cap ends the scan
+
+
+def test_dump_outputs_is_bounded_and_the_same_every_run(tmp_path):
+    """--dump-outputs: an output that fits is written whole; a larger one as a seeded sample (every row at some columns + some whole
+    rows, with their indices) that is the same in every run and stays inside the byte limit.  --steps below 1 is refused."""
+    import numpy as np
+    import pytest
+    import torch
+    bench = _load("bench_for_test7", "bench.py")
+    assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    g = torch.Generator().manual_seed(3)
+    rows = torch.randn((1000, 3000), generator=g)
+    small = torch.randn((10, 4, 3), generator=g)
+    blocks = {"big": [rows[:400], rows[400:]], "small": [small]}
+    limit = 4 << 20
+    for d in ("a", "b"):
+        files = bench.dump_outputs(str(tmp_path / d), blocks, limit=limit)
+        assert sorted(files) == ["big_cols.npy", "big_cols_index.npy", "big_rows.npy", "big_rows_index.npy", "small.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= limit
+    for f in (tmp_path / "a").iterdir():
+        x, y = np.load(f), np.load(tmp_path / "b" / f.name)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    ld = lambda n: np.load(tmp_path / "a" / (n + ".npy"))
+    assert np.array_equal(ld("small"), small.reshape(10, 12).numpy())
+    ri, ci = ld("big_rows_index").astype(np.int64), ld("big_cols_index").astype(np.int64)
+    assert len(ri) > 1 and len(ci) > 1 and np.all(np.diff(ri) > 0) and np.all(np.diff(ci) > 0)
+    assert np.array_equal(ld("big_rows"), rows.numpy()[ri]) and np.array_equal(ld("big_cols"), rows.numpy()[:, ci])

@@ -11,6 +11,10 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 
+# The workers end with gloo's own host-side barrier: dist.barrier() also opens the GPU runtime in every rank, and eight ranks with
+# the GPU open next to the test process exceed what a shared GPU machine allows.
+
+
 def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
@@ -40,7 +44,7 @@ def _worker(rank, world, port, n_clips, frames_per_clip, width, chunk, q):
     per_rank = torch.cat(g.rows(1), 0)
     assert per_rank.shape[0] == counts[1]
     q.put((rank, counts, out.numpy()))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -72,7 +76,11 @@ class _LinearEngine:
         self.mean = torch.tensor(rs.normal(0, 1, self.out_dim).astype(np.float32))
 
     def expand_coef(self, coef, out=None):
-        r = coef @ self.basis + self.mean
+        # the same float32 operations for a row whatever rows come with it, like sdfa_expand_coef (a CPU matmul's kernel -- and so
+        # its last bit -- can depend on the number of rows and on the host's instruction set)
+        r = self.mean.expand(coef.shape[0], self.out_dim)
+        for k in range(self.coef_dim):
+            r = r + coef[:, k:k + 1] * self.basis[k]
         if out is None:
             return r
         out.copy_(r)
@@ -99,7 +107,7 @@ def _expand_worker(rank, world, port, counts_in, chunk, q):
             return coef[f0:f1]
         sd.run_chunks(n, chunk, g, compute)
     q.put((rank, counts, g.gathered().numpy().copy()))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -115,7 +123,7 @@ def test_expand_gather_rebuilds_every_ranks_rows(counts):
     res = [q.get(timeout=120) for _ in procs]
     for p in procs: p.join(timeout=60)
     eng = _LinearEngine()
-    expect = np.concatenate([(torch.tensor(np.random.RandomState(100 + r).normal(0, 1, (counts[r], 5)).astype(np.float32)) @ eng.basis + eng.mean).numpy()
+    expect = np.concatenate([eng.expand_coef(torch.tensor(np.random.RandomState(100 + r).normal(0, 1, (counts[r], 5)).astype(np.float32))).numpy()
                              for r in range(world)])
     for rank, got_counts, out in res:
         assert got_counts == counts
@@ -194,7 +202,7 @@ def _multi_worker(rank, world, port, cases, width, q):
             sd.run_chunks(n, chunk, x, compute)
         out.append((gathered, per_rank, x.gathered().numpy().copy(), n_calls))
     q.put((rank, out))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -220,8 +228,8 @@ def test_gather_modes_at_world_size(world):
     eng = _LinearEngine()
     for ci, (counts, chunk) in enumerate(cases):
         expect = np.concatenate([_rows_of(r, counts[r], width) + 1 for r in range(world)])          # step 1's rows (local + 1)
-        expect_x = np.concatenate([(torch.tensor(np.random.RandomState(100 + r).normal(0, 1, (counts[r], eng.coef_dim)).astype(np.float32)) @ eng.basis
-                                    + eng.mean).numpy().reshape(counts[r], eng.out_dim) for r in range(world)])
+        expect_x = np.concatenate([eng.expand_coef(torch.tensor(np.random.RandomState(100 + r).normal(0, 1, (counts[r], eng.coef_dim)).astype(np.float32)))
+                                   .numpy().reshape(counts[r], eng.out_dim) for r in range(world)])
         for rank, out in res:
             gathered, per_rank, expanded, n_calls = out[ci]
             assert np.array_equal(gathered, expect), (world, ci, rank)

@@ -1,5 +1,5 @@
 # Which HIP stream -> hardware queue assignment lets RCCL's stream run UNDER the compute stream's kernels?  World-size-1 rehearsal
-# traced under three environments.  Usage (GPU box): bash tools/trace_overlap_env.sh <tag>
+# traced under the default environment, a high-priority RCCL stream and a side compute stream.  Usage (GPU box): bash tools/trace_overlap_env.sh <tag>
 TAG=${1:-overlap_env}
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
@@ -16,9 +16,6 @@ run() {
   rm -rf $OUT/$T
 }
 run default ""
-export GPU_MAX_HW_QUEUES=16
-run hwq16 ""
-unset GPU_MAX_HW_QUEUES
 export TORCH_NCCL_HIGH_PRIORITY=1
 run ncclhigh ""
 unset TORCH_NCCL_HIGH_PRIORITY
