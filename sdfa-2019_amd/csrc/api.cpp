@@ -39,6 +39,17 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+}  // namespace
+
+int sdfa_failv(int code, const char *fmt, va_list ap) {
+    char buf[512];
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    g_err = buf;
+    return code;
+}
+
+namespace {
+
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e__ = (expr);                                                                   \

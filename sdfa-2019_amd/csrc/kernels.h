@@ -1,7 +1,12 @@
 // Internal launcher interface between api.cpp (host orchestration) and the .hip kernel files.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdint.h>
+
+// Records the message sdfa_last_error() returns (api.cpp) and returns `code`: the error path of the files with C entry
+// points of their own (render.hip).
+int sdfa_failv(int code, const char *fmt, va_list ap);
 
 enum { ACT_NONE = 0, ACT_LRELU = 1, ACT_TANH = 2 };
 

@@ -4,6 +4,6 @@ Keeps the reference's module / class / method names for the hot path so that
 `python3 -m speech_anime evaluate ...` (evaluate.sh:15-22) and callers of
 `SaberSpeechDrivenAnimation.generate_animation`, `DatasetSlidingWindow.fetch_audio_features` and
 `SpeechDrivenAnimation.forward` keep working; everything arithmetic runs in the HIP library
-(include/sdfa_hip.h).  Training, rendering and the mesh solve are out of scope.
+(include/sdfa_hip.h), the mesh solve and the rendering of the evaluate video included.  Training is out of scope.
 """
 from . import api  # noqa: F401

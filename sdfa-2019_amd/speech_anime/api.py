@@ -41,6 +41,9 @@ def build_model(hparams, state_dict=None):
 def evaluate_model(args):
     from_cli = not isinstance(args, dict)          # python -m speech_anime evaluate: only the files are wanted
     args = args if isinstance(args, dict) else vars(args)
+    if args.get("save_video") and not args.get("template_mesh"):       # before any file or device work
+        raise ValueError("--save_video needs --template_mesh <obj>: the video is rendered from the template mesh (the reference falls "
+                         "back to its bundled FLAME_sample.obj, which is not part of this tree)")
     hparams = configure(args)
     if hparams.eval_input is not None:                                  # api.py:83-87
         rec = [hparams.eval_input]
@@ -67,6 +70,9 @@ def evaluate_model(args):
     return model.evaluate(hparams.trainer.evaluate, experiment=None, in_trainer=False, shard=shard if shard[1] > 1 else None,
                           overwrite_video=args.get("overwrite_video", False),
                           export_mesh_frames=args.get("export_mesh_frames", False), keep_results=not from_cli,
+                          save_video=args.get("save_video", False), grid_w=args.get("grid_w") or 512, grid_h=args.get("grid_h") or 512,
+                          with_title=args.get("with_title", False), draw_truth=args.get("draw_truth", False),
+                          draw_align=args.get("draw_align", False), draw_latent=args.get("draw_latent", False),
                           output_dir=args.get("output_dir") or os.path.join(hparams.get("log_dir") or ".", "evaluate_videos"))
 
 

@@ -51,9 +51,13 @@ def write_wav(path, signal, sr):
     """saber.audio.save (saber/data/audio/io.py:19-24: soundfile.write, 16-bit PCM for a .wav)."""
     from scipy.io import wavfile
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    wavfile.write(path, int(sr), pcm16(signal))
+
+
+def pcm16(signal):
+    """Float signal -> the int16 samples write_wav stores (also the audio track of the evaluate video)."""
     x = np.asarray(signal, np.float32).reshape(-1)
-    pcm = np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)      # libsndfile's float -> int16 conversion clips
-    wavfile.write(path, int(sr), pcm)
+    return np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)      # libsndfile's float -> int16 conversion clips
 
 
 def load_source(path, sr, return_sound=False):

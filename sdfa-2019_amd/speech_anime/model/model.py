@@ -1,8 +1,9 @@
 """SpeechDrivenAnimation / SaberSpeechDrivenAnimation -- inference surface of speech_anime/model/model.py.
 
 Same method names, arguments and result layouts as the reference; the arithmetic is libsdfa_hip.so.
-Not mirrored (out of scope): training (train_step/get_loss), TensorBoard hooks, video rendering and
-the dgrad -> mesh solve (evaluate() writes the dgrad track instead of .obj files / a video).
+Not mirrored (out of scope): training (train_step/get_loss), TensorBoard hooks, titles and the multi-source
+grid of the evaluate video.  evaluate() writes the dgrad track, .obj files with a template mesh and, with save_video, an
+.avi rendered on the GPU (sdfa_amd.render, speech_anime.video).
 """
 import os
 from copy import deepcopy
@@ -261,13 +262,27 @@ class SaberSpeechDrivenAnimation:
                   "phones": None, "latent": None, "latent_align": None, "formants": None}
         return animes, others
 
-    # ---- model.py:121-223 (host loop; rendering / mesh export replaced by a dgrad track dump) ----
+    # ---- model.py:121-223 (host loop: dgrad track dump, mesh export, video rendered on the GPU) ----
     def evaluate(self, sources, experiment=None, in_trainer=False, **kwargs):
         """The reference's host loop over sources (model.py:152-212).  The reference calls generate_animation once per source; here
         the sources are taken in LAUNCH GROUPS -- as many consecutive clips as fit one piece of the engine (`max_frames` animation
         frames; kwargs["group_frames"] overrides) go through ONE generate_animation_batch call -- because frames are independent
         and a clip's rows do not depend on what it is batched with (bitwise, tests/test_surface_fast.py), so every per-clip result
-        and every file written is exactly what the clip-by-clip loop produces, at the batch path's throughput."""
+        and every file written is exactly what the clip-by-clip loop produces, at the batch path's throughput.
+
+        kwargs["save_video"] (the reference's --save_video): also write <output_dir>/<name>.avi, grid_w x grid_h, rendered on the GPU
+        from the template mesh (speech_anime.video); it needs a template (--template_mesh) and fails before any device work without
+        one.  Titles and the truth / latent / alignment panels of the reference's grid are not drawn."""
+        save_video = bool(kwargs.get("save_video", False))
+        if save_video:
+            from .. import viewer
+            if not viewer.has_template():
+                raise ValueError("save_video needs a template mesh (--template_mesh <obj>): the video is rendered from it.  The reference "
+                                 "falls back to its bundled FLAME_sample.obj, which is not part of this tree")
+            skipped = [k for k in ("with_title", "draw_truth", "draw_align", "draw_latent") if kwargs.get(k)]
+            if skipped:
+                print(f"[speech_anime] evaluate: {', '.join(skipped)} not supported: the video shows the inferred face only, without title")
+        video_size = (int(kwargs.get("grid_w") or 512), int(kwargs.get("grid_h") or 512))
         sr = self.hp.audio.sample_rate
         output_dir = kwargs.get("output_dir") or "evaluate_results"
         target_db = kwargs.get("audio_target_db", self.hp.dataset_anime.audio_target_db)
@@ -291,12 +306,12 @@ class SaberSpeechDrivenAnimation:
                 return
             outs = self.generate_animation_batch([g["signal"] for g in group], [g["spk"] for g in group], ensembling_ms=ens, want_inputs=False)
             total = sum(len(o[0]) for o in outs)
-            track_all = eng.last_device_rows(total) if export_frames else None      # one piece: the rows are still on the device
+            track_all = eng.last_device_rows(total) if (export_frames or save_video) else None      # one piece: the rows are still on the device
             f0 = 0
             for g, (tslist, animes, _) in zip(group, outs):
                 track = None if track_all is None else track_all[f0:f0 + len(tslist)]
                 f0 += len(tslist)
-                self._write_result(g, tslist, animes, track, output_dir, export_frames)
+                self._write_result(g, tslist, animes, track, output_dir, export_frames, video_size if save_video else None)
                 if keep:
                     results.append((g["path"], tslist, animes))
             group, group_frames = [], 0
@@ -331,8 +346,9 @@ class SaberSpeechDrivenAnimation:
         flush()
         return results
 
-    def _write_result(self, g, tslist, animes, track, output_dir, export_frames):
-        """One source's files (model.py:195-212): tslist / track dumps, audio.wav, NNNNNN_dgrad.npy and, with a template, NNNNNN.obj."""
+    def _write_result(self, g, tslist, animes, track, output_dir, export_frames, video_size=None):
+        """One source's files (model.py:195-223): tslist / track dumps, audio.wav, NNNNNN_dgrad.npy and, with a template, NNNNNN.obj;
+        with `video_size` = (grid_w, grid_h) also <output_dir>/<name>.avi (viewer.render_video, model.py:214-223)."""
         fps = self.hp.anime.fps
         name = os.path.splitext(os.path.basename(g["path"]))[0]
         out_dir = os.path.join(output_dir, name)
@@ -361,4 +377,32 @@ class SaberSpeechDrivenAnimation:
                     verts, faces = viewer.frames_to_mesh(frames.astype(np.float32), self._face_type)
                 for i_frame in range(len(frames)):
                     viewer.write_obj(os.path.join(out_dir, f"{i_frame:06d}.obj"), verts[i_frame], faces)
-        print(f"[speech_anime] {name}: {len(tslist)} animation frames -> {out_dir} (video rendering is outside this path)")
+        if video_size is not None:
+            video_path = os.path.join(output_dir, name + ".avi")        # model.py:197-203: export_dir = splitext(video_path)[0]
+            self._write_video(video_path, g, tslist, animes, track, video_size)
+            print(f"[speech_anime] {name}: {len(tslist)} animation frames -> {out_dir}, {video_path}")
+        else:
+            print(f"[speech_anime] {name}: {len(tslist)} animation frames -> {out_dir}")
+
+    def _write_video(self, video_path, g, tslist, animes, track, video_size):
+        """viewer.render_video for the inferred source alone (video.py:199-290): frame k is video frame k of the seek plan,
+        seek + solve + render on the GPU, read back in chunks and encoded to MJPEG on host threads, with the 44.1 kHz sound.
+
+        The frame COUNT is the reference's loop (ts accumulated in float64, speech_anime.video.video_frame_count); frame k is
+        blended at k * 1000 / fps like the .obj export (the accumulated ts differs from it by ~1e-12 ms)."""
+        from .. import viewer, video
+        from sdfa_amd.seek import SeekPlan
+        eng = self._model._engine
+        fps = self.hp.anime.fps
+        plan = SeekPlan([tslist], fps, device=eng.device)
+        n = video.video_frame_count(tslist[-1], fps)
+        assert n <= plan.n_queries, (n, plan.n_queries)
+        if track is None:
+            track = torch.from_numpy(np.ascontiguousarray(animes, dtype=np.float32)).to(eng.device).reshape(len(tslist), -1)
+        if self._face_type == "dgrad_3d":
+            verts = viewer.track_to_mesh(track, plan)[:n]
+        else:
+            verts = viewer._device_verts(plan.rows(track)[:n], self._face_type)
+        rend = viewer.renderer(video_size)
+        video.write_video(video_path, n, lambda i0, i1: rend.render(verts[i0:i1]), video_size[0], video_size[1], fps,
+                          sound=g["sound"], sample_rate=_audio.SOUND_SR)

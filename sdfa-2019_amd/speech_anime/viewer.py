@@ -1,6 +1,7 @@
 """Template-mesh state and frame_to_mesh -- the part of speech_anime/viewer/frame.py (:17-141) that turns a
 dgrad / offsets frame into vertices, backed by the GPU deformation solve (sdfa_amd.mesh), including retargeting to a
-template of another topology through triangle correspondences (--mesh_tricorres).  Rendering is out of scope."""
+template of another topology through triangle correspondences (--mesh_tricorres) -- and the rendering of those vertices into
+images on the GPU (render_frame / render_track, sdfa_amd.render; viewer/render_py.py in the reference)."""
 import numpy as np
 import torch
 
@@ -10,6 +11,7 @@ _template_verts, _template_faces = None, None
 _template_c_indices = []
 _template_corres = None
 _solver = None
+_renderers = {}          # (image_size, samples, normals) -> sdfa_amd.render.Renderer of the current template, made on first use
 
 
 def read_obj(path):
@@ -43,6 +45,7 @@ def set_dgrad_static(verts, faces, c_indices=None, corres=None):
     reference pins `non_face.non_face_verts` (frame.py:33) -- 3,762 FLAME vertex indices -- and so does this; a template with
     fewer vertices than those indices address fails here like the reference's native module does on them."""
     global _template_verts, _template_faces, _template_c_indices, _template_corres, _solver
+    _renderers.clear()                   # a renderer is prepared lazily for the new template (renderer())
     _template_verts = np.asarray(verts, np.float32).reshape(-1, 3)
     _template_faces = np.asarray(faces, np.uint32).reshape(-1, 3)
     if c_indices is None:
@@ -98,6 +101,7 @@ def clear_template():
     global _template_verts, _template_faces, _template_c_indices, _template_corres, _solver
     _template_verts = _template_faces = _template_corres = _solver = None
     _template_c_indices = []
+    _renderers.clear()
 
 
 def template_faces():
@@ -129,3 +133,47 @@ def frame_to_mesh(data_frame, face_data_type):
     x = data_frame if torch.is_tensor(data_frame) else torch.from_numpy(np.asarray(data_frame, np.float32))
     verts, faces = frames_to_mesh(x.reshape(1, -1), face_data_type)
     return verts[0], faces
+
+
+def renderer(image_size=(512, 512), samples=4, normals="template"):
+    """The GPU renderer of the current template (render_py.py:31-39 set_template: scale 0.15 / max|template|), one per
+    (image_size, samples, normals), created on first use."""
+    assert _solver is not None, "set_template_mesh first"
+    key = (tuple(int(x) for x in image_size), int(samples), normals)
+    if key not in _renderers:
+        from sdfa_amd.render import Renderer
+        _renderers[key] = Renderer(_template_verts, _template_faces, image_size=key[0], samples=samples, normals=normals,
+                                   device=_solver.device)
+    return _renderers[key]
+
+
+def _device_verts(x, face_data_type):
+    """frames_to_mesh without leaving the device: (n, ...) cuda rows -> (n, V, 3) cuda vertices."""
+    n = x.shape[0]
+    if str(face_data_type).endswith("dgrad_3d"):
+        return _solver.get_mesh(x.reshape(n, -1))
+    if str(face_data_type).endswith("verts_off_3d"):
+        return x.reshape(n, -1, 3) + torch.from_numpy(_template_verts).to(x.device)[None]
+    return x.reshape(n, -1, 3)
+
+
+def render_frame(frame, face_data_type, image_size=(512, 512)):
+    """frame.py:156 render_frame: one dgrad / offsets / vertex frame -> (H, W, 3) uint8 RGB image (numpy)."""
+    assert _solver is not None, "set_template_mesh first"
+    x = frame if torch.is_tensor(frame) else torch.from_numpy(np.asarray(frame, np.float32))
+    x = x.to(device=_solver.device, dtype=torch.float32).reshape(1, -1)
+    return renderer(image_size).render(_device_verts(x, face_data_type))[0].cpu().numpy()
+
+
+def render_track(anime_rows, plan, image_size=(512, 512), face_data_type="dgrad_3d", n=None, samples=4):
+    """model.py:204-223 for one batch of clips as device stages: the animation-rate rows (n_frames, ...) on the GPU and a
+    sdfa_amd.seek.SeekPlan -> images of the first `n` (default: all) video frames, (n, H, W, 3) uint8 cuda.  dgrad: seek + solve +
+    render; offsets: seek, + template, render -- the vertices never leave the device."""
+    assert _solver is not None, "set_template_mesh first"
+    if str(face_data_type).endswith("dgrad_3d"):
+        verts = _solver.get_mesh_seek(anime_rows, plan)
+    else:
+        verts = _device_verts(plan.rows(anime_rows.reshape(anime_rows.shape[0], -1)), face_data_type)
+    if n is not None:
+        verts = verts[:n]
+    return renderer(image_size, samples).render(verts)
