@@ -442,6 +442,31 @@ def test_gemm_variants_agree(eng, golden, variant):
             assert torch.equal(a_, b_)
 
 
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16x6"])
+def test_split_bf16_tile_choice_is_bitwise(synth_sd, mode):
+    """The split-bf16 GEMMs take the 256 x 256 tile where it divides the problem and gives half the CUs a tile, the 128 x 128 tile
+    otherwise (gemm.hip launch_any), so which one a launch gets depends on the batch size and the CU count.  Both tiles do the same
+    products in the same order per accumulator: "gemm_variant" 7 (128 x 128 always) and 12 (256 x 256 wherever it divides) must
+    give the same bits -- z, the attention weights, the PCA coefficients and the rows -- at 1,100 frames (the small launches differ)
+    and at 8,192 (all of them)."""
+    from sdfa_amd import _lib
+    eng = Engine(synth_sd["dgrad"], max_frames=8192, precision=mode)
+    for n in (1100, 8192):
+        x = torch.rand((n, 64, 128, 3), generator=torch.Generator().manual_seed(n)).cuda()
+        spk = torch.arange(n, dtype=torch.int64) % 8
+        res = {}
+        try:
+            for variant in (7, 12):
+                _lib.set_option("gemm_variant", variant)
+                res[variant] = [t.clone() for t in eng.forward(x, spk, want_coef=True)]
+        finally:
+            _lib.set_option("gemm_variant", 0)
+        assert bool(torch.isfinite(res[7][0]).all()) and bool(torch.isfinite(res[7][1]).all()), (mode, n)
+        for what, a, b in zip(("rows", "z", "align", "coef"), res[7], res[12]):
+            assert torch.equal(a, b), (mode, n, what)
+        del res
+
+
 @pytest.mark.parametrize("seed,lstm_gain,flip_bn", [(77, 1.0, False), (4321, 1.3, False), (99, 1.0, True)])
 def test_other_weight_dynamics_vs_the_reference_operators(seed, lstm_gain, flip_bn):
     """The fixtures pin ONE synthetic checkpoint (seed 1234; the pretrained one is not obtainable offline).  VERDICT r3 weak 1(iii): the
@@ -475,7 +500,8 @@ def test_other_weight_dynamics_vs_the_reference_operators(seed, lstm_gain, flip_
     assert torch.equal(z, z2) and torch.equal(align, a2)
 
 
-@pytest.mark.parametrize("mode,tol_z,tol_a", [("fp32", 3e-6, 1e-6), ("bf16x3_attention", 2e-5, 5e-6), ("bf16x6", 3e-6, 1e-6)])
+@pytest.mark.parametrize("mode,tol_z,tol_a", [("fp32", 3e-6, 1e-6), ("bf16x3_attention", 2e-5, 5e-6), ("bf16x6", 3e-6, 1e-6),
+                                              ("bf16_attention", 3e-6, 1e-6)])
 def test_one_pass_attention_agrees_with_the_three_gemm_form(synth_sd, mode, tol_z, tol_a):
     """Round 6: attn_key_score_*_kernel computes key projection + tanh + v-dot in ONE pass over the BiLSTM output (weights in registers,
     tiles through an LDS-DMA ring with hand-counted vmcnt, partial scores per wave) and attn_kernel<true> does softmax + context from the

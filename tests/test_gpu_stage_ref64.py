@@ -1,0 +1,337 @@
+"""Each fp32 stage against a float64 restatement of that stage alone (tests/stage_ref64.py), fed the GPU's own input to the
+stage (the debug taps), at a frame count in every bucket of every launch form the fp32 path picks -- and at full size for the
+one-launch attention layer.
+
+Launch forms by chunk size Nc = round_up(N, 128) and CU count (lstm.hip launch_time_any, attn.hip sdfa_launch_attn_key_score /
+sdfa_attn_fuses_tail):
+  time LSTM    time_lstm_split16_kernel while Nc / 4 <= CUs; time_lstm_split_kernel<2> while Nc / 8 <= CUs;
+               time_lstm_kernel<1> below 8192; time_lstm_kernel<2> from 8192
+  attention    attn_key_score_f32_kernel + attn_kernel<true> (units of 64 >> ts_shift time steps) while Nc / 16 < CUs - CUs / 8;
+               attn_fused_f32_kernel (one launch) from there
+
+Bounds are on max|gpu - ref| / max|ref| of a stage, over every frame of every size.  A bug confined to some frames (a stale
+tile, a unit boundary, the padded tail) or to one step of a recurrence shows at that scale; the sensitivity controls at the
+bottom show that it does.
+
+The debug_keep engine swaps the fused conv stack and the share-map recurrence for their unfused forms; every size here is also
+run through the shipping engine, which must give the same bits.
+
+`python tests/test_gpu_stage_ref64.py` prints the measured errors per stage and size (how the bounds below were set).
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import pytest
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (_HERE, os.path.join(_HERE, "..", "oracle"), os.path.join(_HERE, "..", "sdfa-2019_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+from stage_ref64 import StageRef64                                               # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+# max|gpu - ref| / max|ref| per stage, over every size, the front-end batch and (z, align) the full-size run; each bound is at
+# most 4x the largest value measured on an MI355X (256 CUs), written next to it.  The frequency stage is the largest: its
+# Linear(8192 -> 256) sums 8,192 fp32 products per output (about sqrt(8192) x 6e-8 relative), with no dependence on frame position.
+BOUNDS = {
+    "conv3": 2e-6,       # 5.7e-7
+    "freq": 1e-5,        # 6.6e-6
+    "bilstm": 5e-6,      # 1.8e-6
+    "z": 3e-6,           # 1.0e-6 (full size; 8.8e-7 over the sizes)
+    "align": 1e-5,       # 5.8e-6 (full size; 4.6e-6 over the sizes)
+    "coef": 5e-6,        # 1.4e-6
+    "rows": 4e-6,        # 1.1e-6
+}
+FULL = 8192          # max_frames of both engines: every size below runs in one chunk
+
+
+def round_up(n, m=128):
+    return -(-n // m) * m
+
+
+def time_lstm_form(nc, cus):
+    """The kernel launch_time_any runs for an fp32 chunk of nc frames (no CUs reserved)."""
+    if nc // 4 <= cus:
+        return "time_lstm_split16_kernel"
+    if nc // 8 <= cus:
+        return "time_lstm_split_kernel<2>"
+    return "time_lstm_kernel<2>" if (nc // 64) * 2 >= 256 else "time_lstm_kernel<1>"
+
+
+def attention_form(nc, cus):
+    """The fp32 attention layer's kernels for a chunk of nc frames: the one-launch form, or the two-kernel form and its ts_shift."""
+    if nc // 16 >= cus - cus // 8:
+        return "attn_fused_f32_kernel"
+    ts = 0
+    while ts < 3 and ((nc // 16) << ts) < 2 * cus:
+        ts += 1
+    return f"attn_key_score_f32_kernel+attn_kernel<true> ts_shift={ts}"
+
+
+def sizes_for(cus):
+    """1, 17 and 129 (a short clip, ragged tiles), 8191 and 8192 (time_lstm_kernel<2>, ragged and whole) and, for every edge
+    between the forms that depend on the CU count, the largest frame count at or below it and the smallest above it."""
+    edges = {4 * cus // 128 * 128, 8 * cus // 128 * 128, round_up(16 * (cus - cus // 8)) - 128}
+    out = {1, 17, 129, 8191, 8192}
+    for e in edges:
+        if 128 <= e < FULL:
+            out |= {e, e + 1}
+    return sorted(out)
+
+
+def sampled_frames(n, k=32):
+    """First, last, the 16- and 128-frame tile edges, the real frames of the last (padded) 128-frame tile, then evenly spread."""
+    pick = {0, n - 1, 15, 16, 127, 128}
+    tail0 = (n - 1) // 128 * 128
+    pick |= set(range(max(tail0, n - 16), n))
+    pick = {f for f in pick if 0 <= f < n}
+    spread = k
+    while len(pick) < min(k, n):
+        pick |= set(np.linspace(0, n - 1, spread).astype(int).tolist())
+        spread += 1
+    return np.array(sorted(pick), np.int64)
+
+
+def edge_mask(frames, n):
+    """Frames at a 16-frame unit edge or in the padded last 128-frame tile: where a position-dependent bug would show."""
+    frames = np.asarray(frames)
+    tail = (frames >= (n - 1) // 128 * 128) if n % 128 else np.zeros(len(frames), bool)
+    return (frames % 16 == 0) | (frames % 16 == 15) | tail
+
+
+def frame_err(got, ref):
+    """(max |got - ref| per frame, max |ref|)"""
+    return (got.double() - ref).abs().flatten(1).amax(1).cpu().numpy(), float(ref.abs().max())
+
+
+class Stages:
+    """Per-frame errors of every stage of one size, plus the bitwise comparisons with the shipping engine."""
+
+    def __init__(self, n):
+        self.n = n
+        self.err = {}           # stage -> (frames, per-frame abs err, max|ref|)
+        self.mismatch = []      # what differed from the shipping engine
+
+    def add(self, stage, frames, err, refmax):
+        if stage in self.err:
+            f0, e0, r0 = self.err[stage]
+            frames, err, refmax = np.concatenate([f0, frames]), np.concatenate([e0, err]), max(r0, refmax)
+        self.err[stage] = (np.asarray(frames), np.asarray(err), refmax)
+
+    def rel(self, stage, mask=None):
+        frames, err, refmax = self.err[stage]
+        if mask is not None:
+            m = mask(frames)
+            err = err[m] if m.any() else np.zeros(1)
+        return float(err.max()) / refmax
+
+
+def run_size(ref, keep, ship, feat, spk, table=None):
+    """Both engines on `feat` (one chunk); every stage of the debug_keep run against the float64 stage fed the previous tap."""
+    n = feat.shape[0]
+    st = Stages(n)
+    z, align = keep.encoder(feat)
+    coef, rows = keep.regress(z, spk, want_coef=True)
+    taps = {k: keep.tap(k, n) for k in (1, 2, 3)}
+    for name, args in (("plain", {}), ("table", table)):
+        if args is None:
+            continue
+        z2, a2 = ship.encoder(feat, **args)
+        c2, r2 = ship.regress(z2, spk, want_coef=True)
+        for what, a, b in (("z", z, z2), ("align", align, a2), ("coef", coef, c2), ("rows", rows, r2)):
+            if not torch.equal(a, b):
+                st.mismatch.append(f"{name}:{what}")
+        del z2, a2, c2, r2
+    fr = sampled_frames(n)
+    fi = torch.from_numpy(fr).to(feat.device)
+    st.add("conv3", fr, *frame_err(taps[1][fi], ref.conv_stack(feat[fi])))
+    st.add("freq", np.arange(n), *frame_err(taps[2], ref.freq(taps[1])))
+    st.add("bilstm", np.arange(n), *frame_err(taps[3], ref.bilstm(taps[2])))
+    zr, ar = ref.attention(taps[3])
+    st.add("z", np.arange(n), *frame_err(z, zr))
+    st.add("align", np.arange(n), *frame_err(align, ar))
+    st.add("coef", np.arange(n), *frame_err(coef, ref.regress(z, spk)))
+    for f0 in range(0, n, 1024):
+        sl = slice(f0, min(n, f0 + 1024))
+        st.add("rows", np.arange(sl.start, sl.stop), *frame_err(rows[sl], ref.expand(coef[sl])))
+    keep_host = dict(tap2=taps[2][:32].cpu(), tap3=taps[3][:32].cpu(), z=z[:32].cpu(), coef=coef[:32].cpu(), rows=rows[:32].cpu())
+    return st, keep_host
+
+
+def random_batch(n, seed):
+    rs = np.random.RandomState(seed)
+    feat = torch.from_numpy(rs.uniform(0, 1, (n, 64, 128, 3)).astype(np.float32)).cuda()
+    spk = torch.from_numpy(rs.permutation(np.arange(n) % 8)).cuda()
+    return feat, spk
+
+
+def measure(sd):
+    """Every size of sizes_for(CUs), random features and mixed speakers; one front-end batch with its frame table."""
+    from sdfa_amd import synth
+    from sdfa_amd.engine import Engine
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ref = StageRef64(sd, device="cuda:0")
+    keep = Engine(sd, max_frames=FULL, debug_keep=True)
+    ship = Engine(sd, max_frames=FULL)
+    out = dict(cus=cus, sizes={}, host=None)
+    for n in sizes_for(cus):
+        feat, spk = random_batch(n, 7000 + n)
+        out["sizes"][n], host = run_size(ref, keep, ship, feat, spk)
+        if n == 129:
+            out["host"] = host
+        del feat, spk
+    # real front-end features: speechlike and sweep clips of several lengths, at 16 kHz, with the frame table (column sharing)
+    pcms = [synth.make_pcm(c, L, kind) for c, (L, kind) in enumerate([(48000, "speechlike"), (32000, "sweep"), (40000, "speechlike"),
+                                                                      (24000, "sweep"), (56000, "speechlike"), (36000, "sweep")])]
+    feat, _, _ = ship.mel_frontend(pcms, 16000)
+    fc, fs, hop = ship.last_frame_table
+    spk = torch.arange(feat.shape[0], device="cuda:0") % 8
+    out["frontend"], _ = run_size(ref, keep, ship, feat, spk, table=dict(frame_clip=fc, frame_start=fs, hop=hop))
+    out["forms"] = {n: (time_lstm_form(round_up(n), cus), attention_form(round_up(n), cus)) for n in out["sizes"]}
+    return out
+
+
+@pytest.fixture(scope="module")
+def measured(synth_sd):
+    t0 = time.time()
+    torch.cuda.reset_peak_memory_stats()
+    out = measure(synth_sd["dgrad"])
+    torch.cuda.synchronize()
+    out["seconds"] = time.time() - t0
+    out["peak_bytes"] = torch.cuda.max_memory_allocated()
+    return out
+
+
+def table(out):
+    """Per stage and size: max relative error over all frames, over edge / padded-tail frames, over the rest."""
+    lines = [f"CUs {out['cus']}  ({out.get('seconds', 0):.0f} s, peak {out.get('peak_bytes', 0) / 2**30:.1f} GiB)"]
+    runs = list(out["sizes"].items()) + [("frontend", out["frontend"])]
+    for stage in BOUNDS:
+        for n, st in runs:
+            nn = st.n
+            lines.append(f"{stage:7s} {str(n):>8s}  all {st.rel(stage):.2e}  edge {st.rel(stage, lambda f: edge_mask(f, nn)):.2e}  "
+                         f"rest {st.rel(stage, lambda f: ~edge_mask(f, nn)):.2e}")
+    return "\n".join(lines)
+
+
+def test_sizes_hit_every_launch_form(measured):
+    cus = measured["cus"]
+    forms = measured["forms"]
+    lstm = {f[0] for f in forms.values()}
+    attn = {f[1] for f in forms.values()}
+    every_lstm = {time_lstm_form(nc, cus) for nc in range(128, FULL + 1, 128)}
+    every_attn = {attention_form(nc, cus) for nc in range(128, FULL + 1, 128)}
+    assert lstm == every_lstm and attn == every_attn, (forms, every_lstm, every_attn)
+    if cus == 256:
+        assert sorted(forms) == [1, 17, 129, 1024, 1025, 2048, 2049, 3456, 3457, 8191, 8192]
+    print("\n" + "\n".join(f"{n:5d}  {a}  {b}" for n, (a, b) in sorted(forms.items())))
+
+
+def test_debug_keep_engine_gives_the_shipping_bits(measured):
+    """z, align, coef and rows of the debug_keep engine (unfused conv, unshared recurrence) equal the default engine's, at every
+    size; for the front-end batch also through the frame table (share map, shared layer-0 projection)."""
+    bad = {n: st.mismatch for n, st in list(measured["sizes"].items()) + [("frontend", measured["frontend"])] if st.mismatch}
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("stage", list(BOUNDS))
+def test_stage_against_float64(measured, stage):
+    print("\n" + table(measured))
+    worst = {n: measured["sizes"][n].rel(stage) for n in measured["sizes"]}
+    worst["frontend"] = measured["frontend"].rel(stage)
+    assert max(worst.values()) <= BOUNDS[stage], (stage, worst)
+
+
+# ---------------------------------------------------------------------------------------------------------------- full size
+@pytest.fixture(scope="module")
+def full_size(synth_sd):
+    """The 32 x 10 s batch of tests/test_gpu_fullsize.py (20,352 frames): one multi-chunk call of the shipping engine, and the
+    same frames as three single-chunk debug_keep calls."""
+    from sdfa_amd import synth
+    from sdfa_amd.engine import Engine
+    sd = synth_sd["dgrad"]
+    L = 160000
+    ship = Engine(sd, max_frames=FULL)
+    pcms = [synth.make_pcm(c, L) for c in range(30)] + [synth.make_pcm(3, L), np.zeros(L, np.float32)]
+    feat, _, _ = ship.mel_frontend(pcms, 16000)
+    n = feat.shape[0]
+    spk = torch.arange(n, device="cuda:0") % 8
+    z, align = ship.encoder(feat)
+    _, rows = ship.regress(z, spk)
+    del ship
+    keep = Engine(sd, max_frames=FULL, debug_keep=True)
+    ref = StageRef64(sd, device="cuda:0")
+    out = dict(n=n, equal=[], z=Stages(n), align=None)
+    for f0 in range(0, n, FULL):
+        sl = slice(f0, min(n, f0 + FULL))
+        zk, ak = keep.encoder(feat[sl])
+        _, rk = keep.regress(zk, spk[sl])
+        out["equal"].append((torch.equal(zk, z[sl]), torch.equal(ak, align[sl]), torch.equal(rk, rows[sl])))
+        del rk
+        zr, ar = ref.attention(keep.tap(3, sl.stop - sl.start))
+        out["z"].add("z", np.arange(sl.start, sl.stop), *frame_err(zk, zr))
+        out["z"].add("align", np.arange(sl.start, sl.stop), *frame_err(ak, ar))
+    return out
+
+
+def test_full_size_single_chunk_calls_give_the_multi_chunk_bits(full_size):
+    assert full_size["n"] == 20352
+    assert full_size["equal"] == [(True, True, True)] * 3, full_size["equal"]
+
+
+def test_full_size_one_launch_attention_against_float64(full_size):
+    """All 20,352 frames' z and attention weights against the float64 attention of the BiLSTM output the kernel read."""
+    st = full_size["z"]
+    print(f"\nfull size: z {st.rel('z'):.2e}  align {st.rel('align'):.2e}  (peak device memory so far {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB)")
+    assert st.rel("z") <= BOUNDS["z"] and st.rel("align") <= BOUNDS["align"]
+
+
+# ------------------------------------------------------------------------------------------------------ sensitivity controls
+def test_bounds_catch_a_stale_attention_tile(measured, synth_sd):
+    """One 16-frame unit reading time step t+1 in place of t: the GPU's z misses that reference by more than the bound."""
+    h = measured["host"]
+    ref = StageRef64(synth_sd["dgrad"])
+    good, _ = ref.attention(h["tap3"])
+    bad, _ = ref.attention(h["tap3"], stale=(16, 40))
+    scale = float(good.abs().max())
+    miss = (h["z"].double() - bad).abs().amax(1) / scale
+    assert float(miss[:16].max()) <= BOUNDS["z"] and float(miss[16:].max()) > BOUNDS["z"], miss
+
+
+def test_bounds_catch_a_dropped_recurrent_term(measured, synth_sd):
+    """One step of one direction of the time LSTM without its h feedback: the GPU's BiLSTM output misses it by more than the bound."""
+    h = measured["host"]
+    ref = StageRef64(synth_sd["dgrad"])
+    good = ref.bilstm(h["tap2"])
+    scale = float(good.abs().max())
+    for drop in ((0, 0, 20), (1, 1, 50)):
+        bad = ref.bilstm(h["tap2"], drop_h=drop)
+        assert float((h["tap3"].double() - bad).abs().max()) / scale > BOUNDS["bilstm"], drop
+
+
+def test_bounds_catch_a_missing_mean_term(measured, synth_sd):
+    """One output column without its PCA mean: the GPU's rows miss that reference by more than the bound, in every frame."""
+    h = measured["host"]
+    ref = StageRef64(synth_sd["dgrad"])
+    good = ref.expand(h["coef"])
+    j = int(ref.row_means().abs().argmax())
+    bad = ref.expand(h["coef"], drop_mean=j)
+    miss = (h["rows"].double() - bad)[:, j].abs() / float(good.abs().max())
+    assert float(miss.min()) > BOUNDS["rows"], miss
+
+
+if __name__ == "__main__":
+    from sdfa_amd import synth
+    t0 = time.time()
+    torch.cuda.reset_peak_memory_stats()
+    res = measure(synth.make_state_dict("dgrad", 1234))
+    torch.cuda.synchronize()
+    res["seconds"], res["peak_bytes"] = time.time() - t0, torch.cuda.max_memory_allocated()
+    print(table(res))
+    print(json.dumps({"forms": res["forms"], "mismatch": {str(n): st.mismatch for n, st in res["sizes"].items()},
+                      "frontend_frames": res["frontend"].n, "frontend_mismatch": res["frontend"].mismatch}))
