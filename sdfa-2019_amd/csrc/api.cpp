@@ -1,5 +1,6 @@
 // C ABI of libsdfa_hip.so (include/sdfa_hip.h): host orchestration, weight packing, workspace layout.
 #include "../../include/sdfa_hip.h"
+#include "../../include/sdfa_stream.h"
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -379,11 +380,27 @@ int pack_fc(sdfa_model *m, Packer &pk, const std::string &key, int P, int Kin, b
     return SDFA_OK;
 }
 
+// Frame idx + 1 of sdfa_frame_index, a function of idx alone (the loop there counts idx up from -1.0 in exact steps of 1.0).
+struct FramePos { float fs; int64_t s, e; int32_t ts; };
+FramePos frame_pos(double idx, int sample_rate, int fps, int64_t sliding, int ts_delta_ms) {
+    FramePos f;
+    // frame_to_sample: np.float32(float(idx * sr) / float(fps))          speech_anime.py:141-145
+    f.fs = (float)((idx * (double)sample_rate) / (double)fps);
+    const int64_t mid = (int64_t)std::floor((double)f.fs);
+    f.e = mid + sliding / 2; f.s = f.e - sliding;
+    // sample_to_ms: np.float32(float(((s+e)/2) * 1000.0) / float(sr)); then float32 - ts_delta; round half even
+    const float ms = (float)(((((double)(f.s + f.e)) / 2.0) * 1000.0) / (double)sample_rate);
+    const float shifted = ms - (float)ts_delta_ms;
+    f.ts = (int32_t)std::nearbyintf(shifted);
+    return f;
+}
+
 }  // namespace
 
 extern "C" {
 
 int sdfa_abi_version(void) { return SDFA_ABI_VERSION; }
+int sdfa_stream_abi_version(void) { return SDFA_STREAM_ABI_VERSION; }
 const char *sdfa_last_error(void) { return g_err.c_str(); }
 
 // ------------------------------------------------------------------------------------------------
@@ -397,17 +414,12 @@ int64_t sdfa_frame_index(int64_t n_samples, int sample_rate, int fps, int win, i
     int64_t count = 0;
     double idx = -1.0;
     for (;;) {
-        // frame_to_sample: np.float32(float(idx * sr) / float(fps))          speech_anime.py:141-145
-        const float fs = (float)((idx * (double)sample_rate) / (double)fps);
+        const FramePos f = frame_pos(idx, sample_rate, fps, sliding, ts_delta_ms);
         // frame_in_range: float32 + int -> float32                           sliding_window.py:320-322
-        const float lhs = fs + (float)sliding;
+        const float lhs = f.fs + (float)sliding;
         if (!((double)lhs <= (double)(n_samples + 2 * sliding))) break;
-        const int64_t mid = (int64_t)std::floor((double)fs);
-        const int64_t e = mid + sliding / 2, s = e - sliding;
-        // sample_to_ms: np.float32(float(((s+e)/2) * 1000.0) / float(sr)); then float32 - ts_delta; round half even
-        const float ms = (float)(((((double)(s + e)) / 2.0) * 1000.0) / (double)sample_rate);
-        const float shifted = ms - (float)ts_delta_ms;
-        const int32_t ts = (int32_t)std::nearbyintf(shifted);
+        const int64_t s = f.s, e = f.e;
+        const int32_t ts = f.ts;
         const int64_t lo = s > 0 ? s : 0, hi = e < n_samples ? e : n_samples;
         if (hi > lo && s < 0 && e > n_samples)
             return fail(SDFA_ESHORTCLIP, "signal length %lld != %lld.", (long long)(hi - lo - s), (long long)sliding);
@@ -534,6 +546,97 @@ int sdfa_mel_frontend_gather(const float *d_pcm, const int64_t *d_clip_off, cons
     float *table = reinterpret_cast<float *>(reinterpret_cast<char *>(d_workspace) + w.table_off);
     HIP_TRY(sdfa_launch_mel_columns(c, d_pcm, d_clip_off, d_clip_len, d_frame_clip, d_frame_start, sa.col_src, sa.counts, table, s));
     HIP_TRY(sdfa_launch_gather_features(table, sa.col_to_u, n_frames, w.Nc, sa.frame_major, d_audio_feat, s));
+    return SDFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Live streams (include/sdfa_stream.h)
+int64_t sdfa_stream_frame_positions(int64_t k0, int64_t count, int sample_rate, int fps, int win, int hop, int ts_delta_ms,
+                                    int64_t *h_starts, int32_t *h_tslist) {
+    if (k0 < 0 || count < 0 || sample_rate <= 0 || fps <= 0 || win <= 0 || hop <= 0) return fail(SDFA_EINVAL, "bad stream_frame_positions arguments");
+    const int64_t sliding = (int64_t)hop * 63 + win;
+    for (int64_t i = 0; i < count; ++i) {
+        const FramePos f = frame_pos((double)(k0 + i) - 1.0, sample_rate, fps, sliding, ts_delta_ms);
+        if (h_starts) h_starts[i] = f.s;
+        if (h_tslist) h_tslist[i] = f.ts;
+    }
+    return count;
+}
+
+int64_t sdfa_stream_final_frames(int64_t n_samples, int sample_rate, int fps, int win, int hop) {
+    if (n_samples < 0 || sample_rate <= 0 || fps <= 0 || win <= 0 || hop <= 0) return fail(SDFA_EINVAL, "bad stream_final_frames arguments");
+    if (n_samples > 0x1fffffff) return fail(SDFA_EINVAL, "frame_index: clips of more than 2^29 - 1 samples are not supported (%lld given)", (long long)n_samples);
+    const int64_t sliding = (int64_t)hop * 63 + win;
+    // final: e_k < n, one sample past the window (include/sdfa_stream.h); none while n - 1 < sliding
+    const int64_t m = n_samples - 1;
+    if (m < sliding) return 0;
+    // e_k does not decrease with k (a float32 rounding of an increasing value): the largest k with e_k <= n, by bisection
+    auto end_of = [&](int64_t k) { return frame_pos((double)k - 1.0, sample_rate, fps, sliding, 0).e; };
+    int64_t lo = 0, hi = m * fps / sample_rate + 3;                // e_lo <= m < e_hi
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        (end_of(mid) <= m ? lo : hi) = mid;
+    }
+    return lo + 1;
+}
+
+int sdfa_stream_ring_append(float *d_rings, int r, int32_t n_rings, const int64_t *d_seg, int32_t n_seg, const float *d_src,
+                            int64_t n_src, void *stream) {
+    if (n_seg == 0) return SDFA_OK;
+    if (!d_rings || !d_seg || !d_src || n_seg < 0 || n_rings <= 0 || n_src < 0 || r < 1 || r > 28)
+        return fail(SDFA_EINVAL, "stream_ring_append: null pointer or bad count");
+    HIP_TRY(sdfa_launch_ring_append(d_rings, r, n_rings, d_seg, n_seg, d_src, n_src, (hipStream_t)stream));
+    return SDFA_OK;
+}
+
+int sdfa_mel_frontend_ring(const float *d_rings, int r, int32_t n_rings, const int64_t *d_view_ring, const int64_t *d_view_hi,
+                           int32_t n_views, const int32_t *d_frame_view, const int64_t *d_frame_start, int64_t n_frames,
+                           int sample_rate, float *d_audio_feat, void *d_workspace, int64_t workspace_bytes, void *stream) {
+    if (n_frames == 0) return SDFA_OK;
+    if (!d_rings || !d_view_ring || !d_view_hi || !d_frame_view || !d_frame_start || !d_audio_feat || !d_workspace || n_rings <= 0 ||
+        n_views <= 0 || n_frames < 0)
+        return fail(SDFA_EINVAL, "mel_frontend_ring: null pointer or bad count");
+    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat) & 15) return fail(SDFA_EINVAL, "mel_frontend_ring: pointers must be 16-byte aligned");
+    // the offline call's column transform at 16 kHz is column_mel_r8 in every form but "mel_fft_radix4" (the radix-4 transform of rounds
+    // 2-3, which rounds differently): with that switch on, a live frame could not equal the offline frame, so the call is refused
+    if (g_sdfa_mel_fft_radix4 && (int)(0.064 * sample_rate) == 1024)
+        return fail(SDFA_EINVAL, "mel_frontend_ring: the \"mel_fft_radix4\" option is on; live frames are bit-equal to the default offline transform only");
+    const FeWs w = fe_layout(n_frames);
+    if (workspace_bytes < w.total)
+        return fail(SDFA_ENOSPACE, "mel_frontend_ring: workspace of %lld bytes, %lld needed for %lld frames", (long long)workspace_bytes,
+                    (long long)w.total, (long long)n_frames);
+    if (w.Mc >= (int64_t)1 << 31) return fail(SDFA_EINVAL, "mel_frontend_ring: too many frames in one call");
+    FrontendConsts c;
+    {
+        std::lock_guard<std::mutex> lk(g_fe_mu);
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        auto key = sample_rate * 64 + dev;
+        auto it = g_fe.find(key);
+        if (it == g_fe.end()) {
+            FrontendCache fc;
+            int rc = build_frontend(sample_rate, fc);
+            if (rc) return rc;
+            it = g_fe.emplace(key, fc).first;
+        }
+        c = it->second.c;
+    }
+    if (r < 1 || r > 28 || ((int64_t)1 << r) < (int64_t)c.hop * 63 + c.win)
+        return fail(SDFA_EINVAL, "mel_frontend_ring: rings of 2^%d samples cannot hold a window of %d samples (r <= 28)", r, c.hop * 63 + c.win);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t *sh = reinterpret_cast<int32_t *>(d_workspace);
+    ShareArgs sa{};
+    sa.frame_clip = d_frame_view; sa.frame_start = d_frame_start; sa.hop = c.hop;
+    sa.t_lo = 1; sa.t_hi = 63;
+    sa.frame_major = 1;
+    sa.N = n_frames; sa.Nc = w.Nc; sa.Mc = w.Mc;
+    sa.counts = reinterpret_cast<int64_t *>(sh);
+    sa.prev = sh + 16; sa.shift = sa.prev + w.Nc;
+    HIP_TRY(hipMemsetAsync(sh + 8, 0, sizeof(int32_t), s));      // the status word, as sdfa_mel_frontend_gather
+    HIP_TRY(sdfa_launch_share_prev(sa, s));
+    HIP_TRY(sdfa_launch_mel_ring(c, d_rings, r, n_rings, d_view_ring, d_view_hi, d_frame_view, d_frame_start, sa.prev, sa.shift, n_frames,
+                                 g_sdfa_frontend_stream_block, g_sdfa_frontend_stream_slots, g_sdfa_frontend_stream_phases ? 0 : 1,
+                                 g_sdfa_frontend_stream_spin_max, sh + 8, d_audio_feat, s));
     return SDFA_OK;
 }
 

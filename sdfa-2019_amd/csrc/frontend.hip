@@ -336,12 +336,54 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t clip_buffer(const float *base,
     return __builtin_amdgcn_make_buffer_rsrc((void *)xuni, 0, __builtin_amdgcn_readfirstlane(len * 4), 0x00020000);
 }
 
+// Sample addressing of the column transforms, a compile-time policy (mel_stream_body, column_mel_r4, column_mel_r8).  Either way a
+// sample at position g reads as zero outside [0, len) -- len = the clip's length, or the valid_hi of a ring view -- selected AFTER an
+// unconditional request (the reasons are above clip_buffer).  The request index is picked inside the MC_REQ macros by a condition
+// on the constant Addr::RING, with the clip's clamp spelt out there: as a helper call the same clamp was scheduled differently in
+// mel_stream_repair_kernel<1024>, and the existing kernels are meant to compile to the same code.
+//   ClipAddr  the clip as a buffer of its own samples, clip-relative 32-bit indices clamped into [0, len)
+//   RingAddr  a view of a per-stream ring of R = 2^r samples (include/sdfa_stream.h): the descriptor covers the ring and its mirror
+//             (the first SDFA_STREAM_RING_MIRROR samples repeated behind it, so that a run of WIN + 2 samples never wraps); a sample's
+//             address is its absolute stream position & (R - 1) in 32 bits.  clip_off of a view = ring index | delay << 32; a ring
+//             index outside [0, n_rings) gets an empty descriptor (its requests return 0 and never leave the ring array).
+// ClipAddr::view / RingAddr::view bind the policy to one clip / view.  The unclamped run (column_mel_r8) is taken exactly when the
+// offline call would take it for the same column -- p >= 1 and p + WIN < len in the clip's own coordinates -- because the two forms
+// of that transform do not round alike: a column's bits depend on its form as well as on its samples.
+struct ClipAddr {
+    static constexpr bool RING = false;
+    __device__ __forceinline__ ClipAddr view(int64_t) const { return *this; }
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer(const float *pcm, int64_t off, int len) const { return clip_buffer(pcm + off, len); }
+    __device__ __forceinline__ unsigned wrap(int) const { return 0u; }
+    // samples p - 1 .. p + n lie inside [0, len): one unclamped run, its first dword at byte voff(p, 0)
+    __device__ __forceinline__ bool run(int64_t p, int n, int len) const { return p >= 1 && p + n < (int64_t)len; }
+    __device__ __forceinline__ unsigned voff(int64_t p, int lane) const { return (unsigned)((int)p - 1 + 2 * lane) * 4u; }
+};
+constexpr int RING_MIRROR = 2048;   // include/sdfa_stream.h SDFA_STREAM_RING_MIRROR: >= WIN + 2 at both rates
+struct RingAddr {
+    static constexpr bool RING = true;
+    int mask;       // R - 1
+    int n_rings;
+    int lo;         // 1 - the view's delay: a run starts at p >= lo (p >= 1 in the delayed clip's coordinates)
+    __device__ __forceinline__ RingAddr view(int64_t v) const { return RingAddr{mask, n_rings, 1 - (int)(v >> 32)}; }
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer(const float *pcm, int64_t off, int) const {
+        const int ring = (int)(off & 0xffffffff);
+        const bool ok = (unsigned)ring < (unsigned)n_rings;
+        const int stride = mask + 1 + RING_MIRROR;
+        return clip_buffer(pcm + (ok ? (int64_t)ring * stride : 0), ok ? stride : 0);
+    }
+    __device__ __forceinline__ unsigned wrap(int g) const { return (unsigned)(g & mask); }
+    // len = the view's valid_hi: the offline clip's length in the view's coordinates (or a bound below it that no run reaches)
+    __device__ __forceinline__ bool run(int64_t p, int n, int len) const { return p >= lo && p + n < (int64_t)len; }
+    __device__ __forceinline__ unsigned voff(int64_t p, int lane) const { return (unsigned)((((int)p - 1) & mask) + 2 * lane) * 4u; }
+};
+
 // One wave, one STFT column at sample position p of a clip (radix-4 / LDS-staged FFT): samples with the pre-emphasis applied on
 // the fly -> mel[bb] for band lane + 64 bb.  raw0: the column is a window's column 0, whose very first sample is not pre-emphasised
 // (misc.py:17).  A function of (clip samples, p, raw0) alone: whichever kernel, batch or neighbour computes it, the bits are the same.
-template <int WIN>
+template <int WIN, class Addr = ClipAddr>
 __device__ __forceinline__ void column_mel_r4(const __amdgpu_buffer_rsrc_t xrs, int len, int64_t p, bool raw0, float2 *buf, const float2 *sTw,
-                                              const float *sHamm, const int *sBin0, const float (*sW8)[128], int lane, float (&mel)[2]) {
+                                              const float *sHamm, const int *sBin0, const float (*sW8)[128], int lane, float (&mel)[2],
+                                              const Addr A = Addr()) {
     constexpr int M = WIN / 2, NR4 = M / 256;
     float2 v[NR4][4];
 #pragma unroll
@@ -354,7 +396,7 @@ __device__ __forceinline__ void column_mel_r4(const __amdgpu_buffer_rsrc_t xrs, 
             // requests are unconditional, at clamped indices: a load behind a divergent condition compiles to branch + load +
             // wait, which serialised the requests of a column into ~10 memory round trips
             const int g0 = (int)(p + i), last = len - 1;
-#define MC_REQ(idx) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (unsigned)((idx) < 0 ? 0 : ((idx) > last ? last : (idx))) * 4u, 0, 0))
+#define MC_REQ(idx) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (Addr::RING ? A.wrap(idx) : (unsigned)((idx) < 0 ? 0 : ((idx) > last ? last : (idx)))) * 4u, 0, 0))
             const float rm = MC_REQ(g0 - 1), r0 = MC_REQ(g0), r1 = MC_REQ(g0 + 1);
 #undef MC_REQ
             const float xm = (unsigned)(g0 - 1) < (unsigned)len ? rm : 0.f;
@@ -497,8 +539,10 @@ __device__ __forceinline__ void fft512_r8_to_mel(f32x2 (&v)[8], f32x2 *buf, cons
 }
 
 // One wave, one STFT column of the 16 kHz geometry (WIN = 1024) at sample position p of a clip: see column_mel_r4.
+template <class Addr = ClipAddr>
 __device__ __forceinline__ void column_mel_r8(const __amdgpu_buffer_rsrc_t xrs, int len, int64_t p, bool raw0, f32x2 *buf, const float2 *sTw,
-                                              const float *sHamm, const int *sBin0, const float (*sW8)[128], int lane, float (&mel)[2]) {
+                                              const float *sHamm, const int *sBin0, const float (*sW8)[128], int lane, float (&mel)[2],
+                                              const Addr A = Addr()) {
     constexpr int WIN = 1024;
     f32x2 v[8];
     // A column that lies inside its clip with one sample to spare in front (all but the first / last few of a clip: a wave-uniform
@@ -506,10 +550,10 @@ __device__ __forceinline__ void column_mel_r8(const __amdgpu_buffer_rsrc_t xrs, 
     // dword-aligned; the compiler keeps the three that are used: buffer_load_dwordx3).  NB the whole vector is bit-cast to float4:
     // __builtin_bit_cast(float, q.y) on an ELEMENT of the integer vector compiles to element 0 with this clang (ROCm 7.2) -- the
     // first build loaded one dword per element and returned garbage; found by reading the ISA.
-    const bool inside = __builtin_amdgcn_readfirstlane((int)(p >= 1 && p + WIN < (int64_t)len)) != 0;
+    const bool inside = __builtin_amdgcn_readfirstlane((int)A.run(p, WIN, len)) != 0;
     if (inside) {
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const unsigned voff = (unsigned)((int)p - 1 + 2 * lane) * 4u;
+        const unsigned voff = A.voff(p, lane);
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int i = 2 * (lane + 64 * r);
@@ -525,7 +569,7 @@ __device__ __forceinline__ void column_mel_r8(const __amdgpu_buffer_rsrc_t xrs, 
     for (int r = 0; r < 8; ++r) {
         const int i = 2 * (lane + 64 * r);                             // even sample of z[lane + 64 r]
         const int g0 = (int)(p + i), last = len - 1;
-#define MC_REQ(idx) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (unsigned)((idx) < 0 ? 0 : ((idx) > last ? last : (idx))) * 4u, 0, 0))
+#define MC_REQ(idx) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (Addr::RING ? A.wrap(idx) : (unsigned)((idx) < 0 ? 0 : ((idx) > last ? last : (idx)))) * 4u, 0, 0))
         const float rm = MC_REQ(g0 - 1), r0 = MC_REQ(g0), r1 = MC_REQ(g0 + 1);
 #undef MC_REQ
         const float xm = (unsigned)(g0 - 1) < (unsigned)len ? rm : 0.f;
@@ -674,12 +718,13 @@ constexpr int ST_PROD = 12;        // PC form: waves 0..11 transform columns, wa
 // does the call again in the PC = false form (no waits) when *status is not 0 (tests force that with "frontend_stream_spin_max").
 constexpr int ST_SPIN_MAX = 1 << 22;
 
-template <int WIN, bool PC>
+template <int WIN, bool PC, class Addr = ClipAddr>
 __device__ __forceinline__ void mel_stream_body(const FrontendConsts &c, const float *__restrict__ pcm, const int64_t *__restrict__ clip_off,
                                                 const int64_t *__restrict__ clip_len, const int32_t *__restrict__ frame_clip,
                                                 const int64_t *__restrict__ frame_start, const int32_t *__restrict__ prev,
                                                 const int32_t *__restrict__ shift, int64_t n_frames, int B, int G,
-                                                float *__restrict__ out, int *__restrict__ status, int spin_max, unsigned bid) {
+                                                float *__restrict__ out, int *__restrict__ status, int spin_max, unsigned bid,
+                                                const Addr A = Addr()) {
     constexpr int HOP = WIN / 8;
     constexpr int BUF = WIN == 1024 ? MC8_BUF : WIN / 2;          // float2 per wave
     constexpr int NFFT = PC ? ST_PROD : ST_WAVES;                 // waves that transform
@@ -815,7 +860,8 @@ __device__ __forceinline__ void mel_stream_body(const FrontendConsts &c, const f
         const int clip = frame_clip[n0];
         const int64_t len64 = clip_len[clip], p0 = frame_start[n0];
         const int len = (int)(len64 > 0x1fffffff ? 0x1fffffff : len64);
-        const __amdgpu_buffer_rsrc_t xrs = clip_buffer(pcm + clip_off[clip], len);
+        const Addr Av = A.view(clip_off[clip]);
+        const __amdgpu_buffer_rsrc_t xrs = Av.buffer(pcm, clip_off[clip], len);
         // one column job: (member, raw?, stream column) of job q; the wave's jobs come in increasing order, so mi only moves forward
         auto job_of = [&](int q, int &mi, bool &raw, int &k) {
             while (mi + 1 < J && jstart(mi + 1) <= q) ++mi;
@@ -825,8 +871,8 @@ __device__ __forceinline__ void mel_stream_body(const FrontendConsts &c, const f
         };
         auto transform = [&](int mi, bool raw, int k) {
             float mel[2];
-            if constexpr (WIN == 1024) column_mel_r8(xrs, len, p0 + (int64_t)k * HOP, raw, buf, sTw, sHamm, sBin0, sW8, lane, mel);
-            else column_mel_r4<WIN>(xrs, len, p0 + (int64_t)k * HOP, raw, reinterpret_cast<float2 *>(buf), sTw, sHamm, sBin0, sW8, lane, mel);
+            if constexpr (WIN == 1024) column_mel_r8(xrs, len, p0 + (int64_t)k * HOP, raw, buf, sTw, sHamm, sBin0, sW8, lane, mel, Av);
+            else column_mel_r4<WIN>(xrs, len, p0 + (int64_t)k * HOP, raw, reinterpret_cast<float2 *>(buf), sTw, sHamm, sBin0, sW8, lane, mel, Av);
             float *dst = raw ? sRawRow[mi & (ST_RAW - 1)] : sRing[k % ST_RING];
             dst[lane] = mel[0];
             dst[64 + lane] = mel[1];
@@ -949,6 +995,50 @@ __global__ __launch_bounds__(ST_THREADS) void mel_stream_repair_kernel(FrontendC
     }
 }
 
+// ---------------------------------------------------------------------------- live streams (include/sdfa_stream.h)
+// The spectral stream over views of per-stream sample rings: the same body with RingAddr.  A view (stream x main / delayed copy) plays
+// the part of a clip: clip_off = the view's ring index, clip_len = its valid_hi, frame_start = positions in the ring's stream
+// coordinates.  A column therefore reads the samples the offline call reads for the same frame, and its mel bits are the same.
+template <int WIN, bool PC>
+__global__ __launch_bounds__(ST_THREADS) void mel_ring_kernel(FrontendConsts c, const float *__restrict__ rings, RingAddr A, const int64_t *__restrict__ view_ring,
+                                                              const int64_t *__restrict__ view_hi, const int32_t *__restrict__ frame_view,
+                                                              const int64_t *__restrict__ frame_start, const int32_t *__restrict__ prev,
+                                                              const int32_t *__restrict__ shift, int64_t n_frames, int B, int G,
+                                                              float *__restrict__ out, int *__restrict__ status, int spin_max) {
+    mel_stream_body<WIN, PC, RingAddr>(c, rings, view_ring, view_hi, frame_view, frame_start, prev, shift, n_frames, B, G, out, status, spin_max, blockIdx.x, A);
+}
+
+// mel_stream_repair_kernel for the ring views
+template <int WIN>
+__global__ __launch_bounds__(ST_THREADS) void mel_ring_repair_kernel(FrontendConsts c, const float *__restrict__ rings, RingAddr A, const int64_t *__restrict__ view_ring,
+                                                                     const int64_t *__restrict__ view_hi, const int32_t *__restrict__ frame_view,
+                                                                     const int64_t *__restrict__ frame_start, const int32_t *__restrict__ prev,
+                                                                     const int32_t *__restrict__ shift, int64_t n_frames, int B, int G,
+                                                                     float *__restrict__ out, const int *__restrict__ gate, unsigned n_wg) {
+    if (__builtin_amdgcn_readfirstlane(*gate) == 0) return;
+    for (unsigned bid = blockIdx.x; bid < n_wg; bid += gridDim.x) {
+        mel_stream_body<WIN, false, RingAddr>(c, rings, view_ring, view_hi, frame_view, frame_start, prev, shift, n_frames, B, G, out, nullptr, 0, bid, A);
+        __syncthreads();
+    }
+}
+
+// One workgroup per segment seg[4 i .. 4 i + 3] = (ring, first absolute position, count, offset in src): the segment's samples go to
+// positions pos .. pos + count - 1 of the ring, each at (position & (R - 1)), and again into the mirror when that is below RING_MIRROR.  A segment that names a ring outside [0, n_rings), a
+// count outside [0, R] or a source range outside [0, n_src) is skipped whole.
+__global__ __launch_bounds__(256) void ring_append_kernel(float *__restrict__ rings, int r, int n_rings, const int64_t *__restrict__ seg,
+                                                          const float *__restrict__ src, int64_t n_src) {
+    const int64_t ring = seg[4 * (int64_t)blockIdx.x], pos = seg[4 * (int64_t)blockIdx.x + 1];
+    const int64_t count = seg[4 * (int64_t)blockIdx.x + 2], so = seg[4 * (int64_t)blockIdx.x + 3];
+    const int64_t R = (int64_t)1 << r;
+    if ((uint64_t)ring >= (uint64_t)n_rings || count <= 0 || count > R || so < 0 || so > n_src - count) return;
+    float *dst = rings + ring * (R + RING_MIRROR);
+    for (int64_t i = threadIdx.x; i < count; i += 256) {
+        const int64_t q = (pos + i) & (R - 1);
+        dst[q] = src[so + i];
+        if (q < RING_MIRROR) dst[R + q] = src[so + i];              // the mirror behind the ring
+    }
+}
+
 }  // namespace
 
 extern thread_local int g_sdfa_mel_fft_radix4;   // api.cpp ("mel_fft_radix4"): 1 = the radix-4 / LDS-staged column FFT of rounds 2-3 at 16 kHz too
@@ -988,19 +1078,12 @@ hipError_t sdfa_launch_mel_columns(const FrontendConsts &c, const float *pcm, co
     return hipGetLastError();
 }
 
-// The spectral-stream form: one launch behind share_prev_kernel (share.hip).  block = frames per chain-segment block (multiple of 4, <= 256;
-// 0 = the default 144: 12 members per segment at 60 fps -- measured against 96 / 192 / 240, profiles/r05_ab_frontend.txt), slots = workgroups
-// per block (0 = 12: one per chain at 60 fps).
-hipError_t sdfa_launch_mel_stream(const FrontendConsts &c, const float *pcm, const int64_t *clip_off, const int64_t *clip_len,
-                                  const int32_t *frame_clip, const int64_t *frame_start, const int32_t *prev, const int32_t *shift,
-                                  int64_t n_frames, int block, int slots, int producer_consumer, int spin_max, int *status, float *audio_feat, hipStream_t s) {
-    if (n_frames <= 0) return hipSuccess;
-    if (c.nbins_used > 256) return hipErrorInvalidValue;
-    // Frames per block: 144 (12 members per chain segment at 60 fps: measured optimum on the 20,352-frame batch against 96 / 192 / 240,
-    // profiles/r05_ab_frontend.txt) while that still gives every CU two workgroups; below, shorter segments (more redundant columns per
-    // frame, but the call is latency-bound there and idle CUs are worse), not under 48.
-    int B = block;
-    const int G = slots > 0 ? slots : 12;
+// Frames per block: 144 (12 members per chain segment at 60 fps: measured optimum on the 20,352-frame batch against 96 / 192 / 240,
+// profiles/r05_ab_frontend.txt) while that still gives every CU two workgroups; below, shorter segments (more redundant columns per
+// frame, but the call is latency-bound there and idle CUs are worse), not under 48.
+static bool stream_geometry(int64_t n_frames, int block, int slots, int &B, int &G) {
+    B = block;
+    G = slots > 0 ? slots : 12;
     if (B <= 0) {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
@@ -1010,7 +1093,19 @@ hipError_t sdfa_launch_mel_stream(const FrontendConsts &c, const float *pcm, con
             B = (int)(b < 48 ? 48 : (b > 144 ? 144 : b));
         }
     }
-    if (B > ST_BMAX || G > ST_BMAX) return hipErrorInvalidValue;
+    return B <= ST_BMAX && G <= ST_BMAX;
+}
+
+// The spectral-stream form: one launch behind share_prev_kernel (share.hip).  block = frames per chain-segment block (multiple of 4, <= 256;
+// 0 = the default 144: 12 members per segment at 60 fps -- measured against 96 / 192 / 240, profiles/r05_ab_frontend.txt), slots = workgroups
+// per block (0 = 12: one per chain at 60 fps).
+hipError_t sdfa_launch_mel_stream(const FrontendConsts &c, const float *pcm, const int64_t *clip_off, const int64_t *clip_len,
+                                  const int32_t *frame_clip, const int64_t *frame_start, const int32_t *prev, const int32_t *shift,
+                                  int64_t n_frames, int block, int slots, int producer_consumer, int spin_max, int *status, float *audio_feat, hipStream_t s) {
+    if (n_frames <= 0) return hipSuccess;
+    if (c.nbins_used > 256) return hipErrorInvalidValue;
+    int B, G;
+    if (!stream_geometry(n_frames, block, slots, B, G)) return hipErrorInvalidValue;
     const int64_t nblocks = (n_frames + B - 1) / B, nb8 = (nblocks + 7) / 8 * 8;
     const dim3 grid((unsigned)(nb8 * G));
 #define ST_LAUNCH(W, P) hipLaunchKernelGGL((mel_stream_kernel<W, P>), grid, dim3(ST_THREADS), 0, s, c, pcm, clip_off, clip_len, frame_clip, frame_start, prev, \
@@ -1027,6 +1122,41 @@ hipError_t sdfa_launch_mel_stream(const FrontendConsts &c, const float *pcm, con
                                         prev, shift, n_frames, B, G, audio_feat, status, n_wg)
     if (c.win == 1024) ST_REPAIR(1024); else ST_REPAIR(512);
 #undef ST_REPAIR
+    return hipGetLastError();
+}
+
+// The spectral stream over ring views (sdfa_mel_frontend_ring): the same launch geometry, hand-off protocol, status word and repair pass
+// as sdfa_launch_mel_stream.
+hipError_t sdfa_launch_mel_ring(const FrontendConsts &c, const float *rings, int r, int n_rings, const int64_t *view_ring, const int64_t *view_hi,
+                                const int32_t *frame_view, const int64_t *frame_start, const int32_t *prev, const int32_t *shift, int64_t n_frames,
+                                int block, int slots, int producer_consumer, int spin_max, int *status, float *audio_feat, hipStream_t s) {
+    if (n_frames <= 0) return hipSuccess;
+    if (c.nbins_used > 256 || r < 1 || r > 28 || n_rings <= 0) return hipErrorInvalidValue;
+    int B, G;
+    if (!stream_geometry(n_frames, block, slots, B, G)) return hipErrorInvalidValue;
+    const RingAddr A{(1 << r) - 1, n_rings, 1};
+    const int64_t nblocks = (n_frames + B - 1) / B, nb8 = (nblocks + 7) / 8 * 8;
+    const dim3 grid((unsigned)(nb8 * G));
+#define RG_LAUNCH(W, P) hipLaunchKernelGGL((mel_ring_kernel<W, P>), grid, dim3(ST_THREADS), 0, s, c, rings, A, view_ring, view_hi, frame_view, frame_start, \
+                                           prev, shift, n_frames, B, G, audio_feat, status, spin_max > 0 ? spin_max : ST_SPIN_MAX)
+    if (c.win == 1024) { if (producer_consumer) RG_LAUNCH(1024, true); else RG_LAUNCH(1024, false); }
+    else if (c.win == 512) { if (producer_consumer) RG_LAUNCH(512, true); else RG_LAUNCH(512, false); }
+    else return hipErrorInvalidValue;
+#undef RG_LAUNCH
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !producer_consumer || !status) return e;
+    const unsigned n_wg = grid.x, rgrid = n_wg < 256u ? n_wg : 256u;
+#define RG_REPAIR(W) hipLaunchKernelGGL((mel_ring_repair_kernel<W>), dim3(rgrid), dim3(ST_THREADS), 0, s, c, rings, A, view_ring, view_hi, frame_view, \
+                                        frame_start, prev, shift, n_frames, B, G, audio_feat, status, n_wg)
+    if (c.win == 1024) RG_REPAIR(1024); else RG_REPAIR(512);
+#undef RG_REPAIR
+    return hipGetLastError();
+}
+
+hipError_t sdfa_launch_ring_append(float *rings, int r, int n_rings, const int64_t *seg, int n_seg, const float *src, int64_t n_src, hipStream_t s) {
+    if (n_seg <= 0) return hipSuccess;
+    if (r < 1 || r > 28 || n_rings <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ring_append_kernel, dim3((unsigned)n_seg), dim3(256), 0, s, rings, r, n_rings, seg, src, n_src);
     return hipGetLastError();
 }
 

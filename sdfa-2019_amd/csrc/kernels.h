@@ -86,6 +86,11 @@ hipError_t sdfa_launch_mel_columns(const FrontendConsts &c, const float *pcm, co
 hipError_t sdfa_launch_mel_stream(const FrontendConsts &c, const float *pcm, const int64_t *clip_off, const int64_t *clip_len,
                                   const int32_t *frame_clip, const int64_t *frame_start, const int32_t *prev, const int32_t *shift,
                                   int64_t n_frames, int block, int slots, int producer_consumer, int spin_max, int *status, float *audio_feat, hipStream_t s);
+// live streams (include/sdfa_stream.h): the spectral stream over views of per-stream rings of 2^r samples, and the ring append
+hipError_t sdfa_launch_mel_ring(const FrontendConsts &c, const float *rings, int r, int n_rings, const int64_t *view_ring, const int64_t *view_hi,
+                                const int32_t *frame_view, const int64_t *frame_start, const int32_t *prev, const int32_t *shift, int64_t n_frames,
+                                int block, int slots, int producer_consumer, int spin_max, int *status, float *audio_feat, hipStream_t s);
+hipError_t sdfa_launch_ring_append(float *rings, int r, int n_rings, const int64_t *seg, int n_seg, const float *src, int64_t n_src, hipStream_t s);
 hipError_t sdfa_launch_gather_features(const float *mel_table, const int32_t *col_to_u, int64_t n_frames, int64_t Nc, int frame_major,
                                        float *audio_feat, hipStream_t s);   // frame_major: col_to_u is [n][t] (ShareArgs::frame_major)
 

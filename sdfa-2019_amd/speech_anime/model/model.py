@@ -181,6 +181,20 @@ class SaberSpeechDrivenAnimation:
             ensembling_ms = self.hp.ensembling_ms
         return self._animate(signals, speakers, ensembling_ms, want_inputs)
 
+    def animation_stream(self, speaker, emotion=0, frame_id=0, ensembling_ms=None):
+        """generate_animation for audio that arrives in pieces: an object whose push(chunk) and finish() each return
+        (tslist, animes) shaped like generate_animation's; concatenated, they are generate_animation(signal, ...)[:2] of the
+        whole signal, bit for bit.  Frames are returned as soon as their window has arrived (sdfa_amd.live.LiveSession)."""
+        eng = self._model._engine
+        if eng is None:
+            raise RuntimeError("no weights loaded: call load_state_dict first")
+        if isinstance(speaker, str):
+            speaker = self._speakers_dict[speaker]
+        assert isinstance(speaker, (int, np.integer)), f"given index is {speaker}, {type(speaker)}"
+        if ensembling_ms is None:
+            ensembling_ms = self.hp.ensembling_ms
+        return AnimationStream(self, int(speaker), int(ensembling_ms or 0))
+
     def _animate(self, signals, speakers, ensembling_ms, want_inputs):
         from sdfa_amd.engine import frame_index
         eng = self._model._engine
@@ -406,3 +420,36 @@ class SaberSpeechDrivenAnimation:
         rend = viewer.renderer(video_size)
         video.write_video(video_path, n, lambda i0, i1: rend.render(verts[i0:i1]), video_size[0], video_size[1], fps,
                           sound=g["sound"], sample_rate=_audio.SOUND_SR)
+
+
+class AnimationStream:
+    """One live stream of SaberSpeechDrivenAnimation.animation_stream (a one-stream sdfa_amd.live.LiveSession with host copies)."""
+
+    def __init__(self, owner, speaker, ensembling_ms):
+        from sdfa_amd.live import LiveSession
+        self._owner = owner
+        sr = owner.hp.audio.sample_rate
+        self._session = LiveSession(owner._model._engine, 1, sample_rate=sr, host_copy=True, max_ensembling_ms=max(ensembling_ms, 0))
+        self._sid = self._session.open(speaker, ensembling_ms)
+        self._shape = (owner._model._engine.out_dim // 9, 9) if owner._face_type == "dgrad_3d" else None
+
+    def _result(self, res):
+        width = self._owner._model._engine.out_dim
+        ts, rows = res.get(self._sid, (np.empty(0, np.int32), torch.empty((0, width), dtype=torch.float32)))
+        animes = rows.numpy()
+        if self._shape is not None:
+            animes = animes.reshape((animes.shape[0],) + self._shape)
+        return [int(t) for t in ts], animes
+
+    def push(self, chunk):
+        """Samples (float32 in [-1, 1], at the model rate) -> (tslist, animes) of the frames that became final."""
+        if np.size(chunk) == 0:
+            return self._result({})
+        chunk = SaberSpeechDrivenAnimation._check_signal(chunk)
+        self._session.push(self._sid, chunk)
+        return self._result(self._session.step())
+
+    def finish(self):
+        """Ends the stream: (tslist, animes) of the remaining frames, the tail past the end of the audio included."""
+        self._session.close(self._sid)
+        return self._result(self._session.step())
