@@ -23,6 +23,8 @@ def _parser():
             ap.add_argument("--" + name, action="store_true")
         else:
             ap.add_argument("--" + name, type=typ, default=default)
+    # not a reference flag: who encodes the --save_video frames to JPEG (host PIL threads or the GPU; the same bytes)
+    ap.add_argument("--jpeg_encoder", choices=["pil", "gpu"], default="pil")
     return ap
 
 

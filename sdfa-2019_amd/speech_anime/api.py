@@ -71,6 +71,7 @@ def evaluate_model(args):
                           overwrite_video=args.get("overwrite_video", False),
                           export_mesh_frames=args.get("export_mesh_frames", False), keep_results=not from_cli,
                           save_video=args.get("save_video", False), grid_w=args.get("grid_w") or 512, grid_h=args.get("grid_h") or 512,
+                          jpeg_encoder=args.get("jpeg_encoder") or "pil",
                           with_title=args.get("with_title", False), draw_truth=args.get("draw_truth", False),
                           draw_align=args.get("draw_align", False), draw_latent=args.get("draw_latent", False),
                           output_dir=args.get("output_dir") or os.path.join(hparams.get("log_dir") or ".", "evaluate_videos"))

@@ -286,8 +286,13 @@ class SaberSpeechDrivenAnimation:
 
         kwargs["save_video"] (the reference's --save_video): also write <output_dir>/<name>.avi, grid_w x grid_h, rendered on the GPU
         from the template mesh (speech_anime.video); it needs a template (--template_mesh) and fails before any device work without
-        one.  Titles and the truth / latent / alignment panels of the reference's grid are not drawn."""
+        one.  Titles and the truth / latent / alignment panels of the reference's grid are not drawn.  kwargs["jpeg_encoder"]: "pil"
+        (default, host threads) or "gpu" (sdfa_amd.jpeg) encodes the video's frames; both write the same bytes."""
         save_video = bool(kwargs.get("save_video", False))
+        jpeg_encoder = kwargs.get("jpeg_encoder") or "pil"
+        from .. import video as _video
+        if jpeg_encoder not in _video.JPEG_ENCODERS:
+            raise ValueError(f"jpeg_encoder must be one of {_video.JPEG_ENCODERS}, not {jpeg_encoder!r}")
         if save_video:
             from .. import viewer
             if not viewer.has_template():
@@ -325,7 +330,8 @@ class SaberSpeechDrivenAnimation:
             for g, (tslist, animes, _) in zip(group, outs):
                 track = None if track_all is None else track_all[f0:f0 + len(tslist)]
                 f0 += len(tslist)
-                self._write_result(g, tslist, animes, track, output_dir, export_frames, video_size if save_video else None)
+                self._write_result(g, tslist, animes, track, output_dir, export_frames, video_size if save_video else None,
+                                   jpeg_encoder)
                 if keep:
                     results.append((g["path"], tslist, animes))
             group, group_frames = [], 0
@@ -360,7 +366,7 @@ class SaberSpeechDrivenAnimation:
         flush()
         return results
 
-    def _write_result(self, g, tslist, animes, track, output_dir, export_frames, video_size=None):
+    def _write_result(self, g, tslist, animes, track, output_dir, export_frames, video_size=None, jpeg_encoder="pil"):
         """One source's files (model.py:195-223): tslist / track dumps, audio.wav, NNNNNN_dgrad.npy and, with a template, NNNNNN.obj;
         with `video_size` = (grid_w, grid_h) also <output_dir>/<name>.avi (viewer.render_video, model.py:214-223)."""
         fps = self.hp.anime.fps
@@ -393,14 +399,15 @@ class SaberSpeechDrivenAnimation:
                     viewer.write_obj(os.path.join(out_dir, f"{i_frame:06d}.obj"), verts[i_frame], faces)
         if video_size is not None:
             video_path = os.path.join(output_dir, name + ".avi")        # model.py:197-203: export_dir = splitext(video_path)[0]
-            self._write_video(video_path, g, tslist, animes, track, video_size)
+            self._write_video(video_path, g, tslist, animes, track, video_size, jpeg_encoder)
             print(f"[speech_anime] {name}: {len(tslist)} animation frames -> {out_dir}, {video_path}")
         else:
             print(f"[speech_anime] {name}: {len(tslist)} animation frames -> {out_dir}")
 
-    def _write_video(self, video_path, g, tslist, animes, track, video_size):
+    def _write_video(self, video_path, g, tslist, animes, track, video_size, jpeg_encoder="pil"):
         """viewer.render_video for the inferred source alone (video.py:199-290): frame k is video frame k of the seek plan,
-        seek + solve + render on the GPU, read back in chunks and encoded to MJPEG on host threads, with the 44.1 kHz sound.
+        seek + solve + render on the GPU, encoded to MJPEG on host threads (jpeg_encoder="pil", after a readback in chunks) or
+        on the GPU ("gpu", only the JPEG files are read back), with the 44.1 kHz sound.
 
         The frame COUNT is the reference's loop (ts accumulated in float64, speech_anime.video.video_frame_count); frame k is
         blended at k * 1000 / fps like the .obj export (the accumulated ts differs from it by ~1e-12 ms)."""
@@ -419,7 +426,7 @@ class SaberSpeechDrivenAnimation:
             verts = viewer._device_verts(plan.rows(track)[:n], self._face_type)
         rend = viewer.renderer(video_size)
         video.write_video(video_path, n, lambda i0, i1: rend.render(verts[i0:i1]), video_size[0], video_size[1], fps,
-                          sound=g["sound"], sample_rate=_audio.SOUND_SR)
+                          sound=g["sound"], sample_rate=_audio.SOUND_SR, encoder=jpeg_encoder)
 
 
 class AnimationStream:

@@ -5,7 +5,9 @@ The reference writes XVID frames with cv2.VideoWriter, saves the sound next to t
 ffmpeg (video.py:286).  Neither an H.264 nor an MPEG-4 encoder exists in this image, so the video is an AVI 1.0 file written
 here in pure Python: MJPEG frames (PIL, quality 90) and 16-bit mono PCM audio, one audio chunk interleaved after each video
 frame, with an idx1 index.  Any MJPEG-capable player plays it.  The frames themselves come from the GPU rasterizer
-(sdfa_amd.render); host work is JPEG encoding, overlapped with rendering and readback of the next chunk."""
+(sdfa_amd.render); by default host threads encode them with PIL, overlapped with rendering and readback of the next chunk.
+write_video(encoder="gpu") encodes them on the device instead (sdfa_amd.jpeg: the same bytes, only the JPEG files are read
+back)."""
 import io
 import os
 import struct
@@ -162,41 +164,71 @@ def read_avi(path):
     return out
 
 
-def write_video(path, n_frames, render_chunk, width, height, fps, sound=None, sample_rate=SOUND_SR, chunk=32, workers=None):
-    """Render, read back, encode and write `n_frames` frames.  `render_chunk(i0, i1)` returns frames [i0, i1) as a
-    (i1 - i0, height, width, 3) uint8 cuda tensor; chunks are copied into two pinned host buffers on a side stream while
-    the JPEG encoder threads work on the previous chunk.  `sound`: float signal at `sample_rate` (converted like audio.wav)."""
-    import torch
+JPEG_ENCODERS = ("pil", "gpu")
+
+
+def write_video(path, n_frames, render_chunk, width, height, fps, sound=None, sample_rate=SOUND_SR, chunk=32, workers=None,
+                encoder="pil"):
+    """Render, encode and write `n_frames` frames.  `render_chunk(i0, i1)` returns frames [i0, i1) as a
+    (i1 - i0, height, width, 3) uint8 cuda tensor.  `sound`: float signal at `sample_rate` (converted like audio.wav).
+
+    encoder="pil": chunks are copied into two pinned host buffers on a side stream while the JPEG encoder threads work on
+    the previous chunk.  encoder="gpu": each chunk is encoded on the device (sdfa_amd.jpeg, the same bytes) and only the
+    JPEG files are read back; the host writes chunk k - 1 while the device renders and encodes chunk k."""
+    if encoder not in JPEG_ENCODERS:
+        raise ValueError(f"encoder must be one of {JPEG_ENCODERS}, not {encoder!r}")
     audio = None if sound is None else pcm16(sound)
     writer = AviWriter(path, width, height, fps, n_frames, audio, sample_rate)
-    dev = torch.cuda.current_device()
-    bufs = [torch.empty((chunk, height, width, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-    copy_stream = torch.cuda.Stream(device=dev)
-    pending = []               # (futures of one chunk)
     try:
-        with ThreadPoolExecutor(max_workers=workers or min(16, os.cpu_count() or 1)) as pool:
-            def drain(keep):
-                while len(pending) > keep:
-                    for fut in pending.pop(0):
-                        writer.write_jpeg(fut.result())
-            for ci, i0 in enumerate(range(0, n_frames, chunk)):
-                i1 = min(n_frames, i0 + chunk)
-                drain(1)                                  # the buffer this chunk reuses is free once chunk ci-2 is written
-                rgb = render_chunk(i0, i1)
-                buf = bufs[ci % 2]
-                copy_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(copy_stream):
-                    buf[:i1 - i0].copy_(rgb, non_blocking=True)
-                    rgb.record_stream(copy_stream)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-                ev.synchronize()
-                host = buf.numpy()
-                pending.append([pool.submit(encode_jpeg, host[j]) for j in range(i1 - i0)])
-            drain(0)
+        if encoder == "gpu":
+            _encode_gpu(writer, n_frames, render_chunk, width, height, chunk)
+        else:
+            _encode_pil(writer, n_frames, render_chunk, width, height, chunk, workers)
         writer.close()
     except BaseException:
         if not writer._fp.closed:
             writer._fp.close()
         raise
     return writer
+
+
+def _encode_gpu(writer, n_frames, render_chunk, width, height, chunk):
+    from sdfa_amd.jpeg import JpegEncoder
+    enc = JpegEncoder(width, height, JPEG_QUALITY)
+    step = max(1, min(chunk, enc.chunk))
+    done = []                                      # JPEG files of the previous chunk
+    for i0 in range(0, n_frames, step):
+        pending = enc.submit(render_chunk(i0, min(n_frames, i0 + step)))
+        for jpeg in done:
+            writer.write_jpeg(jpeg)
+        done = pending.result()
+    for jpeg in done:
+        writer.write_jpeg(jpeg)
+
+
+def _encode_pil(writer, n_frames, render_chunk, width, height, chunk, workers):
+    import torch
+    dev = torch.cuda.current_device()
+    bufs = [torch.empty((chunk, height, width, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    copy_stream = torch.cuda.Stream(device=dev)
+    pending = []               # (futures of one chunk)
+    with ThreadPoolExecutor(max_workers=workers or min(16, os.cpu_count() or 1)) as pool:
+        def drain(keep):
+            while len(pending) > keep:
+                for fut in pending.pop(0):
+                    writer.write_jpeg(fut.result())
+        for ci, i0 in enumerate(range(0, n_frames, chunk)):
+            i1 = min(n_frames, i0 + chunk)
+            drain(1)                                  # the buffer this chunk reuses is free once chunk ci-2 is written
+            rgb = render_chunk(i0, i1)
+            buf = bufs[ci % 2]
+            copy_stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(copy_stream):
+                buf[:i1 - i0].copy_(rgb, non_blocking=True)
+                rgb.record_stream(copy_stream)
+                ev = torch.cuda.Event()
+                ev.record(copy_stream)
+            ev.synchronize()
+            host = buf.numpy()
+            pending.append([pool.submit(encode_jpeg, host[j]) for j in range(i1 - i0)])
+        drain(0)
