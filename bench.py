@@ -14,8 +14,14 @@ coefficients followed by a local, bit-identical re-expansion of the peers' rows 
 times both before the measurement and uses the faster (reported in `config`).
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the fused frequency-LSTM recurrence freq_lstm_v3_kernel,
-fp32 MFMA), measured live with HIP events on the launch stream; `cpu_baseline` times the CPU port of the reference
-path on the reference's own operator library (oracle/torch_oracle.py, torch CPU) on a bounded sample on rank 0 at N=1.
+fp32 MFMA), measured live with HIP events on the launch stream inside the timed steps.
+
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps, --dump-outputs, the line.  `--full` adds
+everything else, after the timed steps: the front-end stage timed on its own (`frontend`), the checksum of the gathered rows at N > 1
+(`config.gather_checksum_ok`), the optional legs (column sharing, the configs[3] precision modes, the PCIe-inclusive twin, the
+speech_anime surface; at N > 1 only with --all-legs) and `cpu_baseline`, which times the CPU port of the reference path on the
+reference's own operator library (oracle/torch_oracle.py, torch CPU) on a bounded sample on rank 0 at N=1.  A --full run prints the
+headline twice: right after the timed steps and again, complete, as the last line.
 """
 import argparse
 import json
@@ -93,8 +99,9 @@ class Budget:
 
 
 def emit(res, final):
-    """One JSON line on stdout, flushed at once.  The headline goes out TWICE: right after the timed steps (`"partial": true`, the optional
-    blocks and cpu_baseline still null) and again, complete, as the LAST line -- a run that is stopped in between has still said its number."""
+    """One JSON line on stdout, flushed at once.  A plain run says its headline once (`"partial": false`).  A --full run says it TWICE: right
+    after the timed steps (`"partial": true`, the optional blocks and cpu_baseline still null) and again, complete, as the LAST line -- a run
+    that is stopped in between has still said its number."""
     d = dict(res)
     d["partial"] = not final
     print(json.dumps(d), flush=True)
@@ -143,22 +150,28 @@ def parse(argv=None):
                          "few hardware queues; two streams on one queue serialise -- see DESIGN.md section 5)")
     ap.add_argument("--cpu-sample-seconds", type=float, default=10.0)
     ap.add_argument("--budget-s", type=float, default=240.0,
-                    help="wall-clock budget of the whole command, counted from interpreter start: an optional leg (column sharing, the configs[3] "
+                    help="--full: wall-clock budget of the whole command, counted from interpreter start: an optional leg (column sharing, the configs[3] "
                          "modes, the PCIe twin, the surface block) that is not expected to fit is skipped and listed in `legs_skipped`; the "
                          "headline line is printed right after the timed steps and again, complete, as the last line")
     ap.add_argument("--cpu-baseline-cap-s", type=float, default=25.0, help="upper bound on the whole cpu_baseline leg (thread scan + sample)")
     ap.add_argument("--all-legs", action="store_true",
-                    help="at N > 1 also run the optional legs (column sharing, the configs[3] precision modes); by default a multi-GPU "
-                         "run measures the headline only -- nothing optional may stand between an 8-GPU slot and its line")
+                    help="with --full, at N > 1 also run the optional legs (column sharing, the configs[3] precision modes); by default a "
+                         "multi-GPU --full run measures the headline only -- nothing optional may stand between an 8-GPU slot and its line")
     ap.add_argument("--inject-failure", default=None, metavar="LEG",
-                    help="test hook: raise inside the optional leg LEG (column_sharing | bf16x3 | bf16x3_column_sharing | bf16x3_attention | "
-                         "bf16x6) to prove that no optional leg can cost the headline line")
+                    help="test hook (with --full): raise inside the optional leg LEG (column_sharing | bf16x3 | bf16x3_column_sharing | "
+                         "bf16x3_attention | bf16x6) to prove that no optional leg can cost the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the front-end stage timed on its own, the "
+                         "gathered-rows checksum (N > 1), the optional legs and cpu_baseline (each --no-* switch above leaves one out); "
+                         "without it a run sets up, warms up, times the steps, writes --dump-outputs and prints its one line")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; index files float64), "
                          "at most 64 MB in all: an output that does not fit is written as a fixed, seeded sample (see dump_outputs)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full and (a.all_legs or a.inject_failure):
+        ap.error("--all-legs and --inject-failure act on the optional legs, which only a --full run has")
     return a
 
 
@@ -782,7 +795,7 @@ def main():
 
     dt, stages = timed(False)
     gather_check = None
-    if dist_on and (Mode.gatherer is not None or Mode.direct is not None) and Mode.kind in ("dgrad", "expand", "direct"):
+    if a.full and dist_on and (Mode.gatherer is not None or Mode.direct is not None) and Mode.kind in ("dgrad", "expand", "direct"):
         # every rank holds every rank's rows: order-independent integer checksum (bit patterns summed in int64) of each rank's
         # own rows against the same rows as they arrived here
         def cks(t):
@@ -802,16 +815,18 @@ def main():
     # front end: timed separately (same stream, HIP events), outside the headline region but RIGHT BEHIND it -- the chip in the state the
     # steps leave it in (behind the split-bf16 legs, which run at 1.8 GHz, or in a cold process the same kernel reads 5 - 15 % differently)
     # (one untimed call, then the mean of five back to back: inside a step the stage runs hot behind the previous step's kernels; a single
-    # cold call behind the surface block's other models read 3 - 7 % high)
-    eng.mel_frontend_device(pcm, clip_off, clip_len, frame_clip, frame_start, sr, out=feat, gather=(a.frontend == "gather"))
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(5):
+    # cold call behind the surface block's other models read 3 - 7 % high).  --full only: these are runs of their own.
+    fe_ms = None
+    if a.full:
         eng.mel_frontend_device(pcm, clip_off, clip_len, frame_clip, frame_start, sr, out=feat, gather=(a.frontend == "gather"))
-    ev1.record()
-    torch.cuda.synchronize()
-    fe_ms = ev0.elapsed_time(ev1) / 5
-    stages["frontend"] = fe_ms
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(5):
+            eng.mel_frontend_device(pcm, clip_off, clip_len, frame_clip, frame_start, sr, out=feat, gather=(a.frontend == "gather"))
+        ev1.record()
+        torch.cuda.synchronize()
+        fe_ms = ev0.elapsed_time(ev1) / 5
+        stages["frontend"] = fe_ms
 
     # ---- --dump-outputs: what a caller of the timed path holds after its last step (the legs below overwrite these buffers).  With a
     # gatherer, every rank's rows as they arrived on this rank; otherwise this rank's own rows.
@@ -831,13 +846,14 @@ def main():
     n_chunks = (F + a.chunk - 1) // a.chunk
     # one GPU: the budget decides which optional legs run.  N > 1: optional legs run only with --all-legs, and then on EVERY rank or none
     # (a rank that skipped alone would leave its peers waiting in a collective), so the budget admits everything there
-    need_cpu = world == 1 and not a.no_cpu_baseline
+    need_cpu = a.full and world == 1 and not a.no_cpu_baseline
     budget = Budget(a.budget_s if world == 1 else float("inf"), t0=T_PROCESS_START, reserve_s=(a.cpu_baseline_cap_s + 5.0) if need_cpu else 0.0)
     step_s = dt / a.steps
     passes = a.steps + a.warmup
 
-    # ---- the headline line, complete in itself, goes out NOW (rank 0): whatever happens to the optional legs below -- an exception, a hang,
-    # the driver's limit -- the number has been said.  The same dictionary, with the optional blocks filled in, is printed again as the last line.
+    # ---- the headline line, complete in itself, goes out NOW (rank 0).  A plain run ends with it.  With --full, whatever happens to the
+    # optional legs below -- an exception, a hang, an outside time limit -- the number has been said; the same dictionary, with the optional
+    # blocks filled in, is printed again as the last line.
     res = None
     if rank == 0:
         frames_total = F_all * a.steps
@@ -846,7 +862,6 @@ def main():
         flop_per_launch = FLOP_FREQ_LSTM_PER_FRAME * (F / n_chunks)
         achieved = flop_per_launch / (lstm_ms_per_launch * 1e-3) / 1e12
         traffic, traffic_alg, traffic_src = traffic_from_profile(F / n_chunks)
-        fe_cnt, fe_src = frontend_counter_bytes() if (a.frontend == "gather" and sr == 16000 and not a.ragged_seconds and a.seconds == 10.0) else (None, None)
         res = {
             "metric": "animation frames/s/node (10 s@16 kHz clips); max|Δdgrad| vs CPU ref",
             "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -882,19 +897,21 @@ def main():
                          # h_-1 = 0 and are skipped) -- frac_executed is the figure rocprofv3's MfmaUtil should agree with
                          "flop_executed_per_launch": flop_per_launch * FREQ_LSTM_EXECUTED_FRACTION,
                          "frac_executed": round(achieved * FREQ_LSTM_EXECUTED_FRACTION / PEAK_FP32_MFMA_TFLOPS, 4)},
-            "cpu_baseline": None,                                # filled in below (the complete, last line carries it)
             "model_tflops": round(value / world * FLOP_MODEL_PER_FRAME / 1e12, 2),
             "model_frac_of_fp32_mfma_peak": round(value / world * FLOP_MODEL_PER_FRAME / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
-            "frontend": {"ms": round(fe_ms, 3), "frames_per_s": round(F / (fe_ms * 1e-3), 1),
-                         "hbm_gbps_algorithmic": round(F * FRONTEND_BYTES_PER_FRAME / (fe_ms * 1e-3) / 1e9, 1),
-                         "frac_of_hbm_peak": round(F * FRONTEND_BYTES_PER_FRAME / (fe_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4),
-                         # what the HBM counters saw (FETCH_SIZE x 2 + WRITE_SIZE of the stage's two kernels, committed PMC passes) over
-                         # this run's stage time; null when the passes are absent or csrc/frontend.hip has changed since
-                         "hbm_gbps_counters": None if fe_cnt is None else round(F * fe_cnt / (fe_ms * 1e-3) / 1e9, 1),
-                         "frac_of_hbm_peak_counters": None if fe_cnt is None else round(F * fe_cnt / (fe_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4),
-                         "counters_source": fe_src},
             "stage_ms_per_step": {k: round(v, 3) for k, v in stages.items()},
         }
+        if a.full:
+            res["cpu_baseline"] = None                           # filled in below (the complete, last line carries it)
+            fe_cnt, fe_src = frontend_counter_bytes() if (a.frontend == "gather" and sr == 16000 and not a.ragged_seconds and a.seconds == 10.0) else (None, None)
+            res["frontend"] = {"ms": round(fe_ms, 3), "frames_per_s": round(F / (fe_ms * 1e-3), 1),
+                               "hbm_gbps_algorithmic": round(F * FRONTEND_BYTES_PER_FRAME / (fe_ms * 1e-3) / 1e9, 1),
+                               "frac_of_hbm_peak": round(F * FRONTEND_BYTES_PER_FRAME / (fe_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4),
+                               # what the HBM counters saw (FETCH_SIZE x 2 + WRITE_SIZE of the stage's two kernels, committed PMC passes) over
+                               # this run's stage time; null when the passes are absent or csrc/frontend.hip has changed since
+                               "hbm_gbps_counters": None if fe_cnt is None else round(F * fe_cnt / (fe_ms * 1e-3) / 1e9, 1),
+                               "frac_of_hbm_peak_counters": None if fe_cnt is None else round(F * fe_cnt / (fe_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4),
+                               "counters_source": fe_src}
         # north_star: "MFMA utilisation on the attention stage against gfx950 peak" (target >= 40 %): key / query projections (MFMA GEMMs)
         # + the softmax / context tail (vector + HBM), live stage time and the counter figure of the committed pass
         att_util, att_src, att_gemms = attention_counter_util("fp32") if a.precision == "fp32" else (None, None, None)
@@ -906,7 +923,12 @@ def main():
         if dumped is not None:
             res["outputs_dumped"] = {"dir": a.dump_outputs, "files": dumped}
         res["wall_clock"] = dict(budget.report(), headline_at_s=round(budget.elapsed(), 1))
-        emit(res, final=False)
+        emit(res, final=not a.full)
+    if not a.full:
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the legs behind the headline.  Each runs under leg(), which turns an exception into an {"error": ...} entry, puts the engine back
     # into the headline precision and checks that the device still answers -- if it does not, the line is still printed and the process

@@ -211,3 +211,16 @@ def test_dump_outputs_is_bounded_and_the_same_every_run(tmp_path):
     ri, ci = ld("big_rows_index").astype(np.int64), ld("big_cols_index").astype(np.int64)
     assert len(ri) > 1 and len(ci) > 1 and np.all(np.diff(ri) > 0) and np.all(np.diff(ci) > 0)
     assert np.array_equal(ld("big_rows"), rows.numpy()[ri]) and np.array_equal(ld("big_cols"), rows.numpy()[:, ci])
+
+
+def test_full_is_off_by_default_and_the_leg_switches_need_it():
+    """A plain run is the headline alone; everything else is behind --full.  --all-legs and --inject-failure act on the optional legs, so
+    without --full they are refused rather than ignored."""
+    import pytest
+    bench = _load("bench_for_test8", "bench.py")
+    assert bench.parse([]).full is False
+    a = bench.parse(["--full", "--all-legs", "--inject-failure", "bf16x6"])
+    assert a.full and a.all_legs and a.inject_failure == "bf16x6"
+    for argv in (["--all-legs"], ["--inject-failure", "column_sharing"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)

@@ -25,7 +25,7 @@ def _run(*args, expect=0):
 def test_gpus_2_without_a_launcher_starts_its_own_ranks():
     """Two ranks on this box's ONE GPU over gloo (a bookkeeping rehearsal: the collectives' data is staged through the host): the line
     says n_gpus 2, the process group saw 2 ranks, every rank's record is there, and the gathered rows checksum."""
-    lines, res = _run("--gpus", "2", "--backend", "gloo", "--gather", "expand", *SMALL)
+    lines, res = _run("--gpus", "2", "--backend", "gloo", "--gather", "expand", "--full", *SMALL)
     assert len(lines) == 2, res.stdout[-2000:]                             # the early headline line, then the complete one (last)
     early, d = json.loads(lines[0]), json.loads(lines[-1])
     assert early["partial"] is True and d["partial"] is False and early["value"] == d["value"] and early["roofline"] == d["roofline"]
@@ -45,7 +45,7 @@ def test_a_failed_child_is_a_failed_bench():
 
 @pytest.mark.parametrize("leg", ["column_sharing", "bf16x6"])
 def test_an_optional_leg_that_raises_does_not_cost_the_headline(leg):
-    lines, res = _run("--gpus", "1", "--inject-failure", leg, *SMALL)
+    lines, res = _run("--gpus", "1", "--full", "--inject-failure", leg, *SMALL)
     d = json.loads(lines[-1])
     assert d["value"] > 0 and d["dtype"] == "f32" and d["n_gpus"] == 1 and d["roofline"]["frac"] > 0
     assert d["roofline"]["frac_executed"] < d["roofline"]["frac"] and d["config"]["world_size_seen"] == 1
@@ -61,7 +61,7 @@ def test_a_tiny_budget_skips_the_legs_and_both_lines_are_still_printed():
     """`--budget-s` smaller than what the set-up alone takes -- every optional leg AND the cpu_baseline leg are skipped (listed in
     `legs_skipped`), the headline is printed twice (early, then complete as the last line) with the same value."""
     small = [x for x in SMALL if x not in ("--no-cpu-baseline", "--no-host-io", "--no-surface")]
-    lines, res = _run("--gpus", "1", "--budget-s", "1", *small)
+    lines, res = _run("--gpus", "1", "--full", "--budget-s", "1", *small)
     assert len(lines) == 2
     early, d = json.loads(lines[0]), json.loads(lines[-1])
     assert early["partial"] is True and d["partial"] is False and early["value"] == d["value"] > 0 and d["roofline"]["frac"] > 0
@@ -70,3 +70,17 @@ def test_a_tiny_budget_skips_the_legs_and_both_lines_are_still_printed():
     assert d["cpu_baseline"]["value"] is None and "did not fit" in d["cpu_baseline"]["sample"]
     assert "column_sharing" not in d and "surface" not in d and d["mixed_precision"]["value"] is None
     assert d["wall_clock"]["budget_s"] == 1.0 and d["wall_clock"]["legs_s"] == {}
+
+
+def test_a_plain_run_prints_the_headline_once_and_runs_nothing_else():
+    """Without --full a run sets up, warms up, times the steps and prints ONE line with the headline fields: no optional leg, no
+    cpu_baseline, no front-end stage timed on its own -- even when no --no-* switch says so."""
+    small = [x for x in SMALL if not x.startswith("--no-")]
+    lines, res = _run("--gpus", "1", *small)
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["partial"] is False and d["value"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["roofline"]["frac"] > 0
+    for k in ("cpu_baseline", "frontend", "column_sharing", "mixed_precision", "with_h2d_d2h", "surface", "legs_skipped"):
+        assert k not in d, k
+    assert "frontend" not in d["stage_ms_per_step"] and d["wall_clock"]["legs_s"] == {}

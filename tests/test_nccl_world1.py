@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(*extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--clips-per-gpu", "3", "--seconds", "2",
-           "--chunk", "128", "--no-cpu-baseline", "--no-mixed-precision", "--no-column-sharing", "--no-host-io", "--no-surface", "--force-gather", *extra]
+           "--chunk", "128", "--no-cpu-baseline", "--no-mixed-precision", "--no-column-sharing", "--no-host-io", "--no-surface", "--force-gather", "--full", *extra]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)

@@ -1,7 +1,7 @@
 # Repeats the PCIe-inclusive twin in fresh processes: does the probed copy stream (sdfa_amd/streams.py) overlap every time?
 # Usage (GPU box): bash tools/ab_hostio.sh [runs]
 cd $GRAFT_REPO_ROOT
-B="--steps 4 --warmup 1 --no-cpu-baseline --no-mixed-precision --no-surface --no-column-sharing"
+B="--full --steps 4 --warmup 1 --no-cpu-baseline --no-mixed-precision --no-surface --no-column-sharing"
 N=${1:-8}
 for i in $(seq 1 $N); do
   python3 bench.py $B > /tmp/o.json 2>/dev/null

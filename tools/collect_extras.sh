@@ -5,10 +5,10 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-Q="--no-cpu-baseline --no-mixed-precision --no-host-io --no-surface"
+Q="--full --no-cpu-baseline --no-mixed-precision --no-host-io --no-surface"
 # the headline line again, now that profiles/<round>_pmc of THIS tree is installed (roofline.traffic, frontend / attention counter figures live)
-python3 bench.py --steps 5 --warmup 1 > $OUT/bench_final.json 2> $OUT/err.txt; echo final-done
-python3 bench.py --steps 20 --warmup 3 > $OUT/bench_steps20.json 2>> $OUT/err.txt; echo steps20-done
+python3 bench.py --full --steps 5 --warmup 1 > $OUT/bench_final.json 2> $OUT/err.txt; echo final-done
+python3 bench.py --full --steps 20 --warmup 3 > $OUT/bench_steps20.json 2>> $OUT/err.txt; echo steps20-done
 python3 bench.py --sample-rate 8000 $Q > $OUT/bench_8khz.json 2>> $OUT/err.txt; echo 8khz-done
 python3 bench.py --head offsets --ragged-seconds 3,6 --sample-rate 8000 --clips-per-gpu 80 $Q > $OUT/bench_config5.json 2>> $OUT/err.txt; echo config5-done
 python3 bench.py --mesh-stage $Q --no-column-sharing > $OUT/bench_mesh_stage.json 2>> $OUT/err.txt; echo mesh-done

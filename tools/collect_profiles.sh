@@ -7,9 +7,9 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 5 --warmup 1 "$@" > $OUT/bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full --steps 5 --warmup 1 "$@" > $OUT/bench.json 2> $OUT/bench.err
 echo bench-done
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
 echo trace-done
 # counters: headline path only (no column-sharing / mixed-precision passes, whose launches share symbols and grids with it),
 # frequency LSTM in its hardware-dispatched form 8 (freq_lstm_v3_kernel, one workgroup per tile: the grid size tells pmc_summary.py the frame count;

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BASE="--steps 1 --warmup 0 --no-cpu-baseline --no-mixed-precision --no-column-sharing"
+BASE="--full --steps 1 --warmup 0 --no-cpu-baseline --no-mixed-precision --no-column-sharing"
 for SPEC in "$@"; do
   L=${SPEC%%:*}; ARGS=${SPEC#*:}
   P=1

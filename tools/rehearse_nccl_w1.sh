@@ -5,7 +5,7 @@ TAG=${1:-nccl_w1}
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-B="--steps 5 --warmup 2 --no-cpu-baseline --no-mixed-precision --no-column-sharing --no-host-io --no-surface"
+B="--full --steps 5 --warmup 2 --no-cpu-baseline --no-mixed-precision --no-column-sharing --no-host-io --no-surface"
 python3 $R/bench.py $B > $OUT/plain.json 2> $OUT/err.txt
 for G in dgrad expand; do
   python3 $R/bench.py $B --force-gather --gather $G --backend nccl > $OUT/w1_$G.json 2>> $OUT/err.txt

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/hostio_trace
 mkdir -p $OUT
-B="--steps 3 --warmup 1 --no-cpu-baseline --no-mixed-precision --no-surface --no-column-sharing"
+B="--full --steps 3 --warmup 1 --no-cpu-baseline --no-mixed-precision --no-surface --no-column-sharing"
 for i in 1 2 3 4; do
   rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/t$i -o run -- python3 $R/bench.py $B > $OUT/t$i.json 2> $OUT/t$i.err
   python3 - <<PY

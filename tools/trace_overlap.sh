@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="--steps 2 --warmup 1 --no-cpu-baseline --no-mixed-precision --no-column-sharing --no-surface"
+B="--full --steps 2 --warmup 1 --no-cpu-baseline --no-mixed-precision --no-column-sharing --no-surface"
 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/w1 -o run -- python3 $R/bench.py $B --no-host-io --force-gather --gather dgrad --backend nccl > $OUT/w1.json 2> $OUT/w1.err
 echo w1-done
 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/hostio -o run -- python3 $R/bench.py $B > $OUT/hostio.json 2> $OUT/hostio.err
