@@ -9,6 +9,9 @@ operator is a plain float64 matmul / elementwise op on any device.
 
 Pinned to the reference project's fixtures by tests/test_stage_ref64_cpu.py.
 
+Both output heads: `head="dgrad"` (scale / rotation regressors, two PCA inversions interleaved) and `head="offsets"` (three FCs to
+59 coefficients, one PCA inversion to 15,069 columns).
+
 The keyword arguments `drop_h`, `stale` and `drop_mean` perturb the reference the way a subtle kernel bug would (a step that
 loses its recurrent input, a work unit that reads the wrong time step, an output column without its mean term); the GPU tests
 use them to show that their bounds catch such a bug.
@@ -23,20 +26,24 @@ F64 = torch.float64
 
 class StageRef64:
     def __init__(self, state_dict, device="cpu", head="dgrad"):
-        assert head == "dgrad"
+        assert head in ("dgrad", "offsets")
         o = O.Oracle(state_dict, head)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=F64)
         self.device = device
+        self.head = head
         self.w_conv = [tuple(t(x) for x in c) for c in o.conv]                    # w (co, ci, kf), b, bn scale, bn shift
         self.w_freq = [(t(wi), t(wh), t(b)) for wi, wh, b in o.freq]               # bias_ih + bias_hh folded
         self.freq_proj = tuple(t(x) for x in o.freq_proj)
         self.w_bilstm = [[(t(wi), t(wh)) for wi, wh, _ in layer] for layer in o.bilstm]
         self.w_attn = {k: t(v) for k, v in o.attn.items()}
-        self.trunk = [tuple(t(x) for x in wb) for wb in o.trunk]
-        self.scale = [tuple(t(x) for x in wb) for wb in o.scale]
-        self.rotat = [tuple(t(x) for x in wb) for wb in o.rotat]
-        self.pca_s = tuple(t(x) for x in o.pca_s)                                # compT (59856, 85), means (59856,)
-        self.pca_r = tuple(t(x) for x in o.pca_r)                                # compT (29928, 180), means (29928,)
+        self.trunk = [tuple(t(x) for x in wb) for wb in o.trunk]                 # dgrad: _layers.0; offsets: _layers.0 .. 2
+        if head == "dgrad":
+            self.scale = [tuple(t(x) for x in wb) for wb in o.scale]
+            self.rotat = [tuple(t(x) for x in wb) for wb in o.rotat]
+            self.pca_s = tuple(t(x) for x in o.pca_s)                            # compT (59856, 85), means (59856,)
+            self.pca_r = tuple(t(x) for x in o.pca_r)                            # compT (29928, 180), means (29928,)
+        else:
+            self.pca = tuple(t(x) for x in o.pca)                                # compT (15069, 59), means (15069,)
 
     def _in(self, x):
         return torch.as_tensor(x).to(device=self.device, dtype=F64)
@@ -130,12 +137,15 @@ class StageRef64:
 
     @torch.no_grad()
     def regress(self, z, speaker_id):
-        """z (n, 512), speaker ids (n,) -> coef (n, 265) = [scale coefficients (85) | rotation coefficients (180)]."""
+        """z (n, 512), speaker ids (n,) -> dgrad: coef (n, 265) = [scale coefficients (85) | rotation coefficients (180)];
+        offsets: coef (n, 59), Linear + LeakyReLU(0.2) over [z | speaker one-hot], Linear + tanh, Linear."""
         z = self._in(z)
         spk = torch.as_tensor(speaker_id).to(device=self.device, dtype=torch.int64).reshape(-1)
         c = torch.nn.functional.one_hot(spk, 8).to(F64)
         fc = lambda x, wb: x @ wb[0].T + wb[1]
         lrelu = lambda y: torch.nn.functional.leaky_relu(y, 0.2)
+        if self.head == "offsets":
+            return fc(torch.tanh(fc(lrelu(fc(torch.cat([z, c], -1), self.trunk[0])), self.trunk[1])), self.trunk[2])
         hc = torch.cat([lrelu(fc(torch.cat([z, c], -1), self.trunk[0])), c], -1)
         cs = fc(torch.tanh(fc(lrelu(fc(hc, self.scale[0])), self.scale[1])), self.scale[2])
         cr = fc(torch.tanh(fc(lrelu(fc(hc, self.rotat[0])), self.rotat[1])), self.rotat[2])
@@ -143,17 +153,22 @@ class StageRef64:
 
     @torch.no_grad()
     def expand(self, coef, drop_mean=None):
-        """coef (n, 265) -> rows (n, 89784): both PCA inversions, interleaved per triangle as (6 scale, 3 rotation) values.
-        drop_mean: a column of the rows whose mean term is left out."""
+        """dgrad: coef (n, 265) -> rows (n, 89784): both PCA inversions, interleaved per triangle as (6 scale, 3 rotation) values;
+        offsets: coef (n, 59) -> rows (n, 15069), one PCA inversion.  drop_mean: a column of the rows whose mean term is left out."""
         coef = self._in(coef)
         n = coef.shape[0]
-        s = (coef[:, :85] @ self.pca_s[0].T + self.pca_s[1]).reshape(n, -1, 6)
-        r = (coef[:, 85:] @ self.pca_r[0].T + self.pca_r[1]).reshape(n, -1, 3)
-        rows = torch.cat([s, r], -1).reshape(n, -1)
+        if self.head == "offsets":
+            rows = coef @ self.pca[0].T + self.pca[1]
+        else:
+            s = (coef[:, :85] @ self.pca_s[0].T + self.pca_s[1]).reshape(n, -1, 6)
+            r = (coef[:, 85:] @ self.pca_r[0].T + self.pca_r[1]).reshape(n, -1, 3)
+            rows = torch.cat([s, r], -1).reshape(n, -1)
         if drop_mean is not None:
             rows[:, drop_mean] -= self.row_means()[drop_mean]
         return rows
 
     def row_means(self):
         """The mean term of every output column, in the rows' layout."""
+        if self.head == "offsets":
+            return self.pca[1]
         return torch.cat([self.pca_s[1].reshape(-1, 6), self.pca_r[1].reshape(-1, 3)], -1).reshape(-1)

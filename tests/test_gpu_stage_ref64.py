@@ -16,7 +16,12 @@ bottom show that it does.
 The debug_keep engine swaps the fused conv stack and the share-map recurrence for their unfused forms; every size here is also
 run through the shipping engine, which must give the same bits.
 
-`python tests/test_gpu_stage_ref64.py` prints the measured errors per stage and size (how the bounds below were set).
+The offsets head (three FCs to 59 coefficients, the PCA expansion to 15,069 columns) is checked at the same sizes by the section at
+the bottom: its coefficients and rows against float64, the ragged last column tile, rows written through a 4-byte-aligned output
+pointer, and the fp32 GEMM variants bitwise.
+
+`python tests/test_gpu_stage_ref64.py` prints the measured errors per stage and size (how the bounds below were set);
+`python tests/test_gpu_stage_ref64.py offsets` those of the offsets head.
 """
 import json
 import os
@@ -325,8 +330,158 @@ def test_bounds_catch_a_missing_mean_term(measured, synth_sd):
     assert float(miss.min()) > BOUNDS["rows"], miss
 
 
+# ------------------------------------------------------------------------------------------------------------- offsets head
+# The offsets regressor (BASELINE configs[4], bench.py --head offsets): three FCs to 59 coefficients, then the PCA expansion to
+# Q = 15,069 columns through the generic GEMM -- a ragged last column tile (15,069 = 117 x 128 + 93: columns 14,976 .. 15,068 of
+# 128-wide tiles, 14,848 .. of 256-wide ones) and a row stride of 15,069 floats (rows only 4-byte aligned).  Fed random z at every
+# size of sizes_for(CUs); max|gpu - ref| / max|ref| per stage, each bound at most 4x the value measured on an MI355X, next to it.
+BOUNDS_OFFSETS = {
+    "coef": 3e-6,        # 8.4e-7
+    "rows": 1.5e-6,      # 4.5e-7
+    "rows_tail": 1.5e-6, # 3.9e-7: columns 14,848 .. 15,068 alone, normalised by their own max|ref|
+}
+OFF_Q = 15069
+OFF_LD = 15104       # the basis' padded width, round_up(15069, 128) = 59 x 256: the expansion's Qpad
+OFF_TAIL = 14848     # first column of the last 256-wide tile (and before the last 128-wide one, 14,976)
+# The fp32 GEMM variants compared bitwise with the default (gemm.hip launch_any), and the sizes they run at.  The offsets head's
+# GEMMs are the three FCs (Ppad 512, 256, 128; Qpad = Nc) and the expansion (Ppad = Nc, Qpad = 15,104, a bias per column).  2 and 6
+# steer the LDS-tiled kernel's 64 x 64 tile choice at any size.  5 takes launch_big (256 x 256 tiles) only where Ppad and Qpad are
+# multiples of 256: at Nc = 2048 on FC0, FC1 and the expansion, whose last 256-wide tile is the ragged one.  8 takes launch_fat
+# where it fits (OUT_K4, no column bias, no speaker term, K % 64 == 0, Nc % 256 == 0): FC1 at Nc = 2048.  At 1025 frames
+# (Nc = 1152) 5 and 8 launch the default kernels.  Variant 9 is left out: it only acts on tile-major operands, which no GEMM of
+# this head has; 4 is split-bf16 and not bitwise.  (A kernel trace of the 2048-frame call on an MI355X shows gemm_big_kernel for
+# FC0, FC1 and the expansion under 5 and gemm_fat_kernel for FC1 under 8; the default runs gemm_k4_kernel throughout.)
+OFF_VARIANTS = (2, 5, 6, 8)
+OFF_VARIANT_SIZES = (1025, 2048)
+
+
+def regress_into(eng, z, spk, coef, rows):
+    """sdfa_regress_forward into caller-owned coefficient and row buffers (NaN-filled by the caller, so that an element a kernel
+    leaves unwritten cannot compare equal by holding bits an earlier call left in a recycled allocation)."""
+    import ctypes as C
+    from sdfa_amd._lib import lib, check
+    n = z.shape[0]
+    ws = eng.workspace(n)
+    check(lib.sdfa_regress_forward(eng._m, C.c_void_p(z.data_ptr()), C.c_void_p(spk.data_ptr()), n, C.c_void_p(coef.data_ptr()),
+                                   C.c_void_p(rows.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+
+
+def nan_like(n, k):
+    return torch.full((n, k), float("nan"), dtype=torch.float32, device="cuda:0")
+
+
+def measure_offsets(sd):
+    from sdfa_amd import _lib
+    from sdfa_amd.engine import Engine
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ref = StageRef64(sd, device="cuda:0", head="offsets")
+    eng = Engine(sd, max_frames=FULL)
+    assert (eng.coef_dim, eng.out_dim) == (59, OFF_Q)
+    out = dict(cus=cus, sizes={}, host=None, aligned={}, variants={})
+    for n in sizes_for(cus):
+        rs = np.random.RandomState(9000 + n)
+        z = torch.from_numpy(rs.uniform(-0.9, 0.9, (n, 512)).astype(np.float32)).cuda()
+        spk = torch.from_numpy(rs.permutation(np.arange(n) % 8)).cuda()
+        coef, rows = nan_like(n, 59), nan_like(n, OFF_Q)
+        regress_into(eng, z, spk, coef, rows)
+        st = Stages(n)
+        st.add("coef", np.arange(n), *frame_err(coef, ref.regress(z, spk)))
+        tail_err, tail_ref = [], 0.0
+        for f0 in range(0, n, 1024):
+            sl = slice(f0, min(n, f0 + 1024))
+            rr = ref.expand(coef[sl])
+            st.add("rows", np.arange(sl.start, sl.stop), *frame_err(rows[sl], rr))
+            tail_err.append((rows[sl, OFF_TAIL:].double() - rr[:, OFF_TAIL:]).abs().amax(1).cpu().numpy())
+            tail_ref = max(tail_ref, float(rr[:, OFF_TAIL:].abs().max()))
+            del rr
+        st.add("rows_tail", np.arange(n), np.concatenate(tail_err), tail_ref)
+        out["sizes"][n] = st
+        if n == 1025:
+            # rows written through output pointers 4 bytes past an aligned allocation: the regressor's epilogue and expand_coef
+            # (guard elements on both sides, NaN: nothing may be written outside the rows)
+            buf = torch.full((n * OFF_Q + 2,), float("nan"), dtype=torch.float32, device="cuda:0")
+            odd = buf[1:1 + n * OFF_Q].view(n, OFF_Q)
+            eng.regress(z, spk, out=odd)
+            buf2 = torch.full((n * OFF_Q + 4,), float("nan"), dtype=torch.float32, device="cuda:0")
+            odd2 = buf2[3:3 + n * OFF_Q].view(n, OFF_Q)
+            eng.expand_coef(coef, out=odd2)
+            torch.cuda.synchronize()
+            out["aligned"] = dict(ptr_mod16=(odd.data_ptr() % 16, odd2.data_ptr() % 16), regress=torch.equal(odd, rows),
+                                  expand=torch.equal(odd2, rows), guard=bool(torch.isnan(buf[[0, -1]]).all()) and bool(torch.isnan(buf2[[0, 1, 2, -1]]).all()))
+            del buf, buf2, odd, odd2
+            out["host"] = dict(coef=coef[:32].cpu(), rows=rows[:32].cpu())
+        if n in OFF_VARIANT_SIZES:
+            for v in OFF_VARIANTS:
+                cv, rv = nan_like(n, 59), nan_like(n, OFF_Q)
+                try:
+                    _lib.set_option("gemm_variant", v)
+                    regress_into(eng, z, spk, cv, rv)
+                finally:
+                    _lib.set_option("gemm_variant", 0)
+                out["variants"][(n, v)] = (torch.equal(cv, coef), torch.equal(rv, rows))
+                del cv, rv
+        del z, spk, coef, rows
+    return out
+
+
+@pytest.fixture(scope="module")
+def offsets_measured(synth_sd):
+    return measure_offsets(synth_sd["offsets"])
+
+
+def offsets_table(out):
+    lines = [f"offsets head, CUs {out['cus']}"]
+    for n, st in out["sizes"].items():
+        lines.append(f"{n:5d}  coef {st.rel('coef'):.2e}  rows {st.rel('rows'):.2e}  rows of columns {OFF_TAIL}.. {st.rel('rows_tail'):.2e}")
+    lines.append(f"aligned {out['aligned']}  variants {out['variants']}")
+    return "\n".join(lines)
+
+
+def test_offsets_head_against_float64(offsets_measured):
+    """Coefficients and rows at every size; the columns of the last (ragged) tile also on their own scale, so that an error
+    confined to them is not hidden by the larger values elsewhere in the row."""
+    print("\n" + offsets_table(offsets_measured))
+    assert 1025 in offsets_measured["sizes"]
+    for n, st in offsets_measured["sizes"].items():
+        for stage in BOUNDS_OFFSETS:
+            assert st.rel(stage) <= BOUNDS_OFFSETS[stage], (n, stage, st.rel(stage))
+
+
+def test_offsets_rows_through_a_4_byte_aligned_pointer(offsets_measured):
+    a = offsets_measured["aligned"]
+    assert a["ptr_mod16"] == (4, 12), a
+    assert a["regress"] and a["expand"] and a["guard"], a
+
+
+def test_offsets_fp32_gemm_variants_are_bitwise(offsets_measured):
+    """As tests/test_gpu_parity.py::test_gemm_variants_agree for dgrad: the fp32 GEMM choices contract k in the default kernel's
+    order, so not a bit of the coefficients or the rows differs -- at 2048 frames through launch_big (the 256-wide ragged last
+    column tile of the expansion) and launch_fat, which the host-side conditions below show those variants reach there."""
+    for n in OFF_VARIANT_SIZES:
+        assert n in offsets_measured["sizes"], n
+    nc = round_up(2048)
+    assert nc % 256 == 0 and OFF_LD % 256 == 0 and OFF_LD == round_up(OFF_Q) and OFF_TAIL == OFF_LD - 256
+    want = {(n, v): (True, True) for n in OFF_VARIANT_SIZES for v in OFF_VARIANTS}
+    assert offsets_measured["variants"] == want, offsets_measured["variants"]
+
+
+def test_offsets_bound_catches_a_missing_mean_in_the_ragged_tile(offsets_measured, synth_sd):
+    h = offsets_measured["host"]
+    ref = StageRef64(synth_sd["offsets"], head="offsets")
+    good = ref.expand(h["coef"])
+    means = ref.row_means()
+    j = 14976 + int(means[14976:].abs().argmax())
+    miss = (h["rows"].double() - ref.expand(h["coef"], drop_mean=j))[:, j].abs() / float(good.abs().max())
+    assert float(miss.min()) > BOUNDS_OFFSETS["rows"], (j, miss)
+
+
 if __name__ == "__main__":
     from sdfa_amd import synth
+    if sys.argv[1:] == ["offsets"]:
+        print(offsets_table(measure_offsets(synth.make_state_dict("offsets", 1234))))
+        sys.exit(0)
     t0 = time.time()
     torch.cuda.reset_peak_memory_stats()
     res = measure(synth.make_state_dict("dgrad", 1234))

@@ -78,3 +78,48 @@ def test_perturbations_touch_only_what_they_name(chain):
     assert abs(float(diff[:, j].min()) - float(ref.row_means()[j].abs())) <= 1e-12
     diff[:, j] = 0
     assert float(diff.max()) <= 1e-12
+
+
+# ------------------------------------------------------------------------------------------------------------- offsets head
+@pytest.fixture(scope="module")
+def offsets_chain(golden, synth_sd):
+    """The offsets model's stages chained on the fixture's first 4 frames (speaker 2, as tests/test_oracle_golden.py)."""
+    g = golden["model_offsets"]
+    x = torch.from_numpy(golden["model_dgrad"]["audio_feat"][g["audio_feat_index"]])
+    ref = StageRef64(synth_sd["offsets"], head="offsets")
+    z, align = ref.attention(ref.bilstm(ref.freq(ref.conv_stack(x))))
+    coef = ref.regress(z, torch.full((4,), 2))
+    return g, ref, dict(z=z.numpy(), align=align.numpy(), coef=coef.numpy(), rows=ref.expand(coef).numpy())
+
+
+def test_offsets_head_matches_the_reference_fixture(offsets_chain):
+    g, _, st = offsets_chain
+    assert st["coef"].dtype == st["rows"].dtype == np.float64
+    assert np.abs(st["z"] - g["z"][:, 0]).max() <= TOL_ACT
+    assert np.abs(st["align"] - g["align"][:, 0]).max() <= TOL_ALIGN
+    assert st["coef"].shape == (4, 59) and np.abs(st["coef"] - g["coef"][:, 0]).max() <= TOL_ACT
+    assert st["rows"].shape == (4, 15069)
+    assert np.abs(st["rows"][0] - g["offsets_f0"]).max() <= TOL_DGRAD
+    assert np.abs(st["rows"][:, ::7] - g["offsets_stride7"]).max() <= TOL_DGRAD
+    assert np.abs(st["rows"].sum(1) - g["offsets_sum"]).max() <= 15069 * 1e-6
+
+
+def test_offsets_regressor_reads_its_speaker(offsets_chain):
+    """The one-hot speaker code enters the first FC only; another speaker gives other coefficients."""
+    _, ref, st = offsets_chain
+    z = torch.from_numpy(st["z"])
+    c5 = ref.regress(z, torch.full((4,), 5)).numpy()
+    assert np.abs(c5 - st["coef"]).max() > 1e-4
+    mixed = ref.regress(z, torch.tensor([2, 5, 2, 5])).numpy()
+    assert np.abs(mixed[0::2] - st["coef"][0::2]).max() <= 1e-12 and np.abs(mixed[1::2] - c5[1::2]).max() <= 1e-12
+
+
+def test_offsets_missing_mean_touches_only_its_column(offsets_chain):
+    _, ref, st = offsets_chain
+    means = ref.row_means()
+    assert means.shape == (15069,)
+    j = int(means.abs().argmax())
+    diff = (ref.expand(torch.from_numpy(st["coef"]), drop_mean=j) - torch.from_numpy(st["rows"])).abs()
+    assert abs(float(diff[:, j].min()) - float(means[j].abs())) <= 1e-12
+    diff[:, j] = 0
+    assert float(diff.max()) <= 1e-12
