@@ -302,16 +302,15 @@ int sdfa_ensemble_mean(const float *d_a, const float *d_b, int64_t n, float *d_o
  *                      hop by hop (same features, bit for bit; only the order of the mel table's rows differs)
  *   "share_gx0_off"    1 = sdfa_encoder_forward_shared expands the frequency projection to all columns before the layer-0 BiLSTM input
  *                      projection (rounds 2-3) instead of projecting the distinct columns and letting the recurrence read them through the map
- *   "pca_unfused"      1 = the dgrad PCA expansion as two generic GEMM launches with the scatter epilogue (round-1 form)
- *   "conv_unfused"     1 = conv1_pool_kernel + conv23_kernel instead of the fused conv123_kernel (what the debug taps use)
  *   "conv_fp32"        1 = the body precision modes (bf16, bf16x3, bf16x6) keep the conv stack on the fp32 kernel instead of
  *                      conv123_bf16_kernel (NOT bit-identical: that stack's operand rounding)
  *   "pca_fp32"         1 = SDFA_PREC_BF16X3 keeps the dgrad PCA expansion on the fp32 kernel (NOT bit-identical: the expansion's operand rounding)
  *   "attn_unfused"     1 = the attention stage as key-projection GEMM + attn_kernel computing the scores from the stored projections (rounds 1-5)
  *                      instead of attn_key_score_*_kernel (key projection + tanh + v-dot in one pass, nothing stored) + attn_kernel<true>;
  *                      2 = that two-kernel form also where exact fp32 would run the WHOLE layer in one launch (attn_fused_f32_kernel: running
- *                      softmax + context while the tile is in LDS; chunks of about 3,600 frames and more).  The three forms are NOT
- *                      bit-identical to each other (order of a dot product's terms / of the softmax's sums: last-bit differences)
+ *                      softmax + context while the tile is in LDS; chunks of about 3,600 frames and more).  Forms 0 and 2 are
+ *                      bit-identical (the same running-softmax recurrence); form 1 differs from them in the last bits (order of a
+ *                      dot product's terms and of the softmax's sums)
  *   "frontend_two_kernel" 1 = sdfa_mel_frontend_gather as share map + mel_columns_kernel + gather_features_kernel through a mel table in
  *                      HBM (rounds 2-4) instead of the spectral stream (mel_stream_kernel: mel rows in an LDS ring, no table); same bits
  *   "frontend_stream_phases" 1 = the spectral stream's workgroups alternate between transforming a phase's columns and emitting its frames

@@ -735,11 +735,7 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
             // per element pair less (round 4; lstm.hip: lstm_cell_quad<true>).  A weight picks up one more fp32 rounding; the stage
             // stays inside its 1e-4 tap tolerance (tests/test_gpu_parity.py) and all launch forms share the packed weights.
             for (int r = 0; r < 512; ++r) {
-#ifdef SDFA_OLD_CELL   /* A/B build only (make EXP=OLD_CELL): round 3's unscaled weights + cell update */
-                const float k = 1.0f;
-#else
                 const float k = (r / 128 == 2) ? 2.8853900817779268f : 1.4426950408889634f;
-#endif
                 for (int j = 0; j < 64; ++j) cat[(size_t)r * 192 + j] = (*wih)[(size_t)r * 64 + j] * k;
                 for (int j = 0; j < 128; ++j) cat[(size_t)r * 192 + 64 + j] = (*whh)[(size_t)r * 128 + j] * k;
             }
@@ -747,13 +743,8 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
             pack_freq_lstm_bf16(reinterpret_cast<uint16_t *>(&pk.buf[o_flwb]) + (size_t)d * 3 * 24 * 512 * 8, cat.data(), perm.data());
             if (d == 0) first = o;
             else if (o != first + (size_t)48 * 512 * 4) return fail(SDFA_ESTATE, "internal: freq-lstm weights not contiguous");
-            for (int p = 0; p < 512; ++p) {
-#ifdef SDFA_OLD_CELL
-                bias[d * 512 + p] = (*bih)[perm[p]] + (*bhh)[perm[p]];
-#else
+            for (int p = 0; p < 512; ++p)
                 bias[d * 512 + p] = ((*bih)[perm[p]] + (*bhh)[perm[p]]) * ((perm[p] / 128 == 2) ? 2.8853900817779268f : 1.4426950408889634f);
-#endif
-            }
         }
         o_flw = first;
         o_flb = pk.add(1024);
@@ -983,8 +974,6 @@ int64_t sdfa_workspace_bytes(const sdfa_model *m, int64_t max_frames) {
 // documented next to sdfa_debug_set_option in include/sdfa_hip.h.
 extern thread_local int g_sdfa_gemm_variant;
 thread_local int g_sdfa_freq_lstm_shape = 0;
-thread_local int g_sdfa_pca_unfused = 0;
-thread_local int g_sdfa_conv_unfused = 0;
 thread_local int g_sdfa_pca_lds = 0;
 thread_local int g_sdfa_pca_fp32 = 0;     // "pca_fp32": 1 = the dgrad PCA expansion stays on the fp32 kernel in SDFA_PREC_BF16X3 (A/B)
 thread_local int g_sdfa_conv_fp32 = 0;    // "conv_fp32": 1 = the conv stack stays on the fp32 kernel in the mixed-precision modes (A/B)
@@ -1018,8 +1007,6 @@ int sdfa_debug_set_option(const char *name, int value) {
     if (name && !strcmp(name, "time_lstm_split")) { g_sdfa_time_lstm_split = value; return SDFA_OK; }
     if (name && !strcmp(name, "gemm_variant")) { g_sdfa_gemm_variant = value; return SDFA_OK; }
     if (name && !strcmp(name, "freq_lstm_shape")) { g_sdfa_freq_lstm_shape = value; return SDFA_OK; }
-    if (name && !strcmp(name, "pca_unfused")) { g_sdfa_pca_unfused = value; return SDFA_OK; }
-    if (name && !strcmp(name, "conv_unfused")) { g_sdfa_conv_unfused = value; return SDFA_OK; }
     if (name && !strcmp(name, "pca_lds")) { g_sdfa_pca_lds = value; return SDFA_OK; }
     if (name && !strcmp(name, "conv_fp32")) { g_sdfa_conv_fp32 = value; return SDFA_OK; }
     if (name && !strcmp(name, "pca_fp32")) { g_sdfa_pca_fp32 = value; return SDFA_OK; }
@@ -1186,13 +1173,13 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
             ca.col_src = sa.col_src; ca.col_limit = d_ulimit;
         }
         const int conv_terms = g_sdfa_conv_fp32 ? 0 : stage_terms(m, STAGE_BODY);
-        if (m->keep && conv_terms && !g_sdfa_conv_unfused) {
+        if (m->keep && conv_terms) {
             // debug taps in a body precision mode: the X3 tap must be the arithmetic that ships -- conv123_bf16_kernel -- so a
             // packing or K-order bug in pack_conv_bf16 can be localised; the pool1 tap (which the fused kernel never writes) stays fp32
             pf.begin("conv1"); HIP_TRY(sdfa_launch_conv1(ca, s)); pf.end();
             ca.wb = m->cv_wb; ca.terms = conv_terms;
             pf.begin("conv23"); HIP_TRY(sdfa_launch_conv123(ca, s)); pf.end();
-        } else if (m->keep || g_sdfa_conv_unfused) {   // the debug taps read pool1
+        } else if (m->keep) {   // the debug taps read pool1
             pf.begin("conv1"); HIP_TRY(sdfa_launch_conv1(ca, s)); pf.end();
             pf.begin("conv23"); HIP_TRY(sdfa_launch_conv23(ca, s)); pf.end();
         } else {
@@ -1300,7 +1287,7 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
 static hipError_t expand_rows(const sdfa_model *m, const float *coef, int64_t N, int64_t Nc, int64_t f0,
                               float *const *h_d_outs, int n_outs, int *queue, hipStream_t s) {
     float *d_out = h_d_outs[0];
-    if (m->pca_n == 2 && !g_sdfa_pca_unfused) {
+    if (m->pca_n == 2) {
         // dgrad head: both bases in one fp32 kernel (all precision modes) so that every output line is written
         // once, whole (pca.hip)
         PcaArgs pa{};

@@ -231,10 +231,6 @@ __device__ __forceinline__ void ks_split8(const float4 &x0, const float4 &x1, bf
     }
 }
 
-#ifndef SDFA_KS_EXP
-#define SDFA_KS_EXP 0      /* timing experiments only (make EXP=KS_EXP EXPVAL=n; wrong results by design): 1 no MFMAs, 2 no DMA, 3 no split, 4 no tanh */
-#endif
-
 template <int TERMS>
 __global__ __launch_bounds__(512, 2) void attn_key_score_kernel(AttnKeyArgs a) {
     constexpr bool LO = TERMS > 1;
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(512, 2) void attn_key_score_kernel(AttnKeyArgs a) {
     const unsigned ring_lds = (unsigned)(uintptr_t)sRing;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);  // provably wave-uniform: the request's base and M0 must be scalar registers
 #define KS_DMA1(slot, j, gcol)                                                                       \
-    if (SDFA_KS_EXP != 2) {                                                                          \
+    {                                                                                                \
         const char *gb = reinterpret_cast<const char *>(H4 + (int64_t)(4 * (j)) * Mc + (gcol));     \
         const unsigned la = ring_lds + (unsigned)(((slot) * 32 + (j)) * 1024);                      \
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(la), "v"(voff), "s"(gb) : "memory"); \
@@ -347,42 +343,34 @@ __global__ __launch_bounds__(512, 2) void attn_key_score_kernel(AttnKeyArgs a) {
                     if (LO) bl[(s + 1) & 1] = rd[(8 * (s + 1) + 1) * KS_COLS];
                 }
                 if ((s & 3) == 1 && more) KS_DMA1(slotp, wave_u + 8 * (s >> 2), gnext)
-                if (SDFA_KS_EXP != 3) {
-                    const int q = s >> 3;
-                    if ((s & 7) == 0) { xa = rs[(64 * q) * KS_COLS]; xb = rs[(64 * q + 1) * KS_COLS]; }
-                    if ((s & 7) == 2) {
-                        const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+                const int q = s >> 3;
+                if ((s & 7) == 0) { xa = rs[(64 * q) * KS_COLS]; xb = rs[(64 * q + 1) * KS_COLS]; }
+                if ((s & 7) == 2) {
+                    const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) shi[e] = (__bf16)x[e];
-                    }
-                    if ((s & 7) == 4 && LO) {
-                        const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+                    for (int e = 0; e < 8; ++e) shi[e] = (__bf16)x[e];
+                }
+                if ((s & 7) == 4 && LO) {
+                    const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) slo[e] = (__bf16)(x[e] - (float)shi[e]);
-                    }
-                    if ((s & 7) == 6) {
-                        *reinterpret_cast<bf16x8 *>(rs + (64 * q) * KS_COLS) = shi;
-                        if (LO) *reinterpret_cast<bf16x8 *>(rs + (64 * q + 1) * KS_COLS) = slo;
-                    }
+                    for (int e = 0; e < 8; ++e) slo[e] = (__bf16)(x[e] - (float)shi[e]);
+                }
+                if ((s & 7) == 6) {
+                    *reinterpret_cast<bf16x8 *>(rs + (64 * q) * KS_COLS) = shi;
+                    if (LO) *reinterpret_cast<bf16x8 *>(rs + (64 * q + 1) * KS_COLS) = slo;
                 }
                 KS_SB()
-                if (SDFA_KS_EXP != 1) {
-                    if (LO) {
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[s], bh[s & 1], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[s], bl[s & 1], acc, 0, 0, 0);
-                    }
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[s], bh[s & 1], acc, 0, 0, 0);
+                if (LO) {
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[s], bh[s & 1], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[s], bl[s & 1], acc, 0, 0, 0);
                 }
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[s], bh[s & 1], acc, 0, 0, 0);
             }
             KS_SB()
-            float part;
-            if (SDFA_KS_EXP == 4) part = acc[0] + acc[1] + acc[2] + acc[3];
-            else {
-                part = vv.x * tanhf_acc(acc[0] + qb.x);
-                part += vv.y * tanhf_acc(acc[1] + qb.y);
-                part += vv.z * tanhf_acc(acc[2] + qb.z);
-                part += vv.w * tanhf_acc(acc[3] + qb.w);
-            }
+            float part = vv.x * tanhf_acc(acc[0] + qb.x);
+            part += vv.y * tanhf_acc(acc[1] + qb.y);
+            part += vv.z * tanhf_acc(acc[2] + qb.z);
+            part += vv.w * tanhf_acc(acc[3] + qb.w);
             part += __shfl_xor(part, 16);
             part += __shfl_xor(part, 32);
             if (kg == 0) Sw[(col0 + (int64_t)i * Nc + l15) * 8] = part;

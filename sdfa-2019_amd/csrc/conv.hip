@@ -19,18 +19,9 @@ namespace {
 // for s < 0, so max(f(v0), f(v1)) = f(max(v0, v1)) resp. f(min(v0, v1)) BITWISE, and the activation can run once on the selected
 // accumulator.  The select is ONE instruction: v_med3(v0, v1, c) with c = +inf picks the max, c = -inf the min; c = copysign(inf, s)
 // is one v_bfi per channel value.  Six vector instructions per pooled element instead of nine.
-// -DSDFA_CONV_POOL_LATE=1 (make EXP=CONV_POOL_LATE) keeps the activation-on-both-rows order for same-box A/B timing: same bits.
 __device__ __forceinline__ float pool_act(float a0, float a1, float b, float s, float t) {
-#if SDFA_CONV_NOEPI          /* timing experiment only (wrong results): no activation at all -- what is the whole epilogue worth? */
-    return __builtin_amdgcn_fmed3f(a0, a1, __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, s) & 0x80000000u) | 0x7f800000u));
-#elif SDFA_CONV_POOL_LATE
-    const float v0 = lrelu02(a0 + b) * s + t;
-    const float v1 = lrelu02(a1 + b) * s + t;
-    return fmaxf(v0, v1);
-#else
     const float c = __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, s) & 0x80000000u) | 0x7f800000u);
     return lrelu02(__builtin_amdgcn_fmed3f(a0, a1, c) + b) * s + t;
-#endif
 }
 
 // ---------------------------------------------------------------------------------- conv1 + pool
@@ -83,8 +74,8 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(ConvArgs a) {
         for (int s = 0; s < 5; ++s) {
             float b0 = sIn[(2 * p) * 3 + 2 * s + h][l31];
             float b1 = sIn[(2 * p + 1) * 3 + 2 * s + h][l31];
-            acc0 = MFMA(SDFA_OP(wa[s]), SDFA_OP(b0), acc0);
-            acc1 = MFMA(SDFA_OP(wa[s]), SDFA_OP(b1), acc1);
+            acc0 = MFMA(wa[s], b0, acc0);
+            acc1 = MFMA(wa[s], b1, acc1);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -221,13 +212,8 @@ __global__ __launch_bounds__(256, 2) void conv23_kernel(ConvArgs a) {
 // order per output element as the two-kernel path (which stays, for the debug taps): bitwise identical results.
 __global__ __launch_bounds__(256, 2) void conv123_kernel(ConvArgs a) {
     __shared__ float4 sP1[80][32];   // 10 pool1 rows x 32 ci as 80 k-quads
-#if SDFA_CONV_OCC4           /* timing experiment only (wrong results: races): the slice and the constants ALIAS pool1, so four workgroups fit a CU */
-    float (*sIn)[33] = reinterpret_cast<float (*)[33]>(&sP1[40][0]);
-    float (*sPar)[64] = reinterpret_cast<float (*)[64]>(&sP1[70][0]);
-#else
     __shared__ float sIn[68][33];    // input rows k = (f - f_lo) * 3 + c, f_lo = 16 fc - 3; +1 column against bank conflicts
     __shared__ float sPar[6][64];
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
@@ -287,8 +273,8 @@ __global__ __launch_bounds__(256, 2) void conv123_kernel(ConvArgs a) {
             for (int s = 0; s < 5; ++s) {
                 const float b0 = sIn[6 * j + 2 * s + h][l31];
                 const float b1 = sIn[6 * j + 3 + 2 * s + h][l31];
-                acc0 = MFMA(SDFA_OP(w1[s]), SDFA_OP(b0), acc0);
-                acc1 = MFMA(SDFA_OP(w1[s]), SDFA_OP(b1), acc1);
+                acc0 = MFMA(w1[s], b0, acc0);
+                acc1 = MFMA(w1[s], b1, acc1);
             }
             const bool valid = f1 >= 0 && f1 < 64;       // rows -1 and 64 are conv2's zero padding
 #pragma unroll

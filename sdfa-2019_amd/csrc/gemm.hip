@@ -16,10 +16,6 @@
 #include "common.h"
 #include "kernels.h"
 
-#ifdef SDFA_STAMPS
-__device__ unsigned long long g_stamp[8];
-#endif
-
 extern thread_local int g_sdfa_gemm_variant;   // "gemm_variant" option, defined below
 
 namespace {
@@ -167,13 +163,6 @@ __global__ __launch_bounds__(256, WTP != WT ? 3 : (WT == 2 ? 2 : 4)) void gemm_k
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     {
-#ifdef SDFA_STAMPS
-        // DIAGNOSTIC BUILD ONLY (make STAMPS=1): where do a stage's cycles go?  s_memtime around each phase, summed per wave.
-        unsigned long long t0, t1, t2, t3, t4, sum_load = 0, sum_mfma = 0, sum_store = 0, sum_bar = 0;
-#define STAMP(t) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#else
-#define STAMP(t)
-#endif
         GEMM_GLOAD_A(0)
         GEMM_LSTORE_A(0)
         if (nstage > 1) { GEMM_GLOAD_A(1) }
@@ -181,18 +170,10 @@ __global__ __launch_bounds__(256, WTP != WT ? 3 : (WT == 2 ? 2 : 4)) void gemm_k
         int st = 0;
         for (; st + 1 < nstage; st += 2) {
             // even stage: LDS buffer 0 holds tile st, set A holds tile st+1
-            STAMP(t0)
             if (st + 2 < nstage) { GEMM_GLOAD_B(st + 2) }
-            STAMP(t1)
             GEMM_COMPUTE(0)
-            STAMP(t2)
             GEMM_LSTORE_A(1)
-            STAMP(t3)
             __syncthreads();
-            STAMP(t4)
-#ifdef SDFA_STAMPS
-            sum_load += t1 - t0; sum_mfma += t2 - t1; sum_store += t3 - t2; sum_bar += t4 - t3;
-#endif
             // odd stage: LDS buffer 1 holds tile st+1, set B holds tile st+2
             if (st + 3 < nstage) { GEMM_GLOAD_A(st + 3) }
             GEMM_COMPUTE(1)
@@ -200,12 +181,6 @@ __global__ __launch_bounds__(256, WTP != WT ? 3 : (WT == 2 ? 2 : 4)) void gemm_k
             __syncthreads();
         }
         if (st < nstage) { GEMM_COMPUTE(0) }   // odd stage count: the last tile is already in LDS buffer 0
-#ifdef SDFA_STAMPS
-        if (lane == 0 && nstage >= 64) {
-            atomicAdd(&g_stamp[0], sum_load); atomicAdd(&g_stamp[1], sum_mfma); atomicAdd(&g_stamp[2], sum_store);
-            atomicAdd(&g_stamp[3], sum_bar); atomicAdd(&g_stamp[4], (unsigned long long)((nstage + 1) / 2));
-        }
-#endif
     }
 
     // ---------------------------------------------------------------- epilogue
@@ -513,11 +488,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_big_kernel(GemmArgs a) {
     const int c = tid & 255, g0 = tid >> 8;
     const int64_t qrow = a.q_tile_major ? 128 : a.ldq;
     const float4 *Pn = P + p0;
-#ifdef SDFA_GEMM_SAMESLAB   /* timing experiment only: every workgroup streams the SAME column block (cache-resident) */
-    const float4 *Qn = a.q_tile_major ? Q : Q + q0;
-#else
     const float4 *Qn = a.q_tile_major ? Q + (q0 >> 7) * (int64_t)a.q_slab_rows * 128 : Q + q0;
-#endif
     int kin_n = 0;
     const unsigned boffP = (unsigned)((2 * g0 * a.ldp + c) * 16);
     const unsigned boffQ = a.q_tile_major ? (unsigned)((((int64_t)(c >> 7) * a.q_slab_rows + 2 * g0) * 128 + (c & 127)) * 16)
@@ -594,12 +565,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_big_kernel(GemmArgs a) {
     }
     BB_LOADP(0) BB_LOADQ(0) BB_LOADP(1) BB_LOADQ(1) BB_ADVANCE()
     __syncthreads();
-#ifdef SDFA_GEMM_LOADONLY   /* timing experiment only: the operand stream without LDS staging and matrix work */
-    for (int st = 0; st + 2 < nstage; ++st) {
-        acc[0][0][0] += rp[0][0].x + rp[0][1].y + rp[1][0].z + rp[1][1].w + rq[0][0].x + rq[0][1].y + rq[1][0].z + rq[1][1].w;
-        BB_LOADP(0) BB_LOADQ(0) BB_LOADP(1) BB_LOADQ(1) BB_ADVANCE()
-    }
-#else
     // (behind the last stage the registers hold stale operands: they are split and written to the buffer nobody reads any more)
     for (int st = 0; st < nstage; ++st) {
         const int buf = st & 1;
@@ -615,7 +580,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_big_kernel(GemmArgs a) {
         BB_ROW(3) BB_SB() BB_PIECE_B(buf, 3) BB_ADVANCE() BB_SB()
         __syncthreads();
     }
-#endif
 #undef BB_SB
 #undef BB_LOADP
 #undef BB_LOADQ
@@ -756,14 +720,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16x6_big_kernel(GemmArgs a) {
     }
     B6B_GLOAD(rpA, rqA)
     __syncthreads();
-#ifdef SDFA_GEMM6_NOSTAGE   /* timing experiment only: the MFMA + LDS-read loop without the operand stream (wrong results) */
-#undef B6B_GLOAD
-#undef B6B_PAIR
-#undef B6B_WRITE
-#define B6B_GLOAD(RP, RQ)
-#define B6B_PAIR(R, e, HI, MID, LO)
-#define B6B_WRITE(buf, pq, HI, MID, LO)
-#endif
     // (behind the last stage the registers hold stale operands: they are split and written to the buffer nobody reads any more)
     for (int st = 0; st < nstage; st += 2) {
         B6B_STAGE(st, 0, rpA, rqA, rpB, rqB)
@@ -1045,47 +1001,27 @@ __global__ __launch_bounds__(256, 1) void gemm_fat_kernel(GemmArgs a) {
     FAT_READ(SP(0), SQ(0), 1, fa1, fb1)
     FAT_READ(SP(0), SQ(0), 2, fa2, fb2)
     FAT_READ(SP(0), SQ(0), 3, fa3, fb3)
-#ifndef SDFA_FAT_RG
-#define SDFA_FAT_RG 4
-#endif
-#define FAT_RG SDFA_FAT_RG
-#ifndef SDFA_FAT_DG
-#define SDFA_FAT_DG 1
-#endif
-#define FAT_DG SDFA_FAT_DG   /* the 16 DMA requests of a stage in 4 / FAT_DG groups */
 #define FAT_Q(A, B, q)                                                                                           \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = MFMA(SDFA_OP(f4c(A[i], q)), SDFA_OP(f4c(B[j], q)), acc[i][j]);
-#ifdef SDFA_STAMPS
-    unsigned long long ft0 = 0, ft1 = 0, ft2 = 0, ft3 = 0, ft4 = 0, fs_k0 = 0, fs_k12 = 0, fs_bar = 0, fs_last = 0, fs_n = 0, fs_epi = 0, fs_tiles = 0;
-#define FSTAMP(t) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#define FSTAMP_SUM() { fs_k0 += ft1 - ft0; fs_k12 += ft2 - ft1; fs_bar += ft3 - ft2; fs_last += ft4 - ft3; ++fs_n; }
-#else
-#define FSTAMP(t)
-#define FSTAMP_SUM()
-#endif
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = MFMA(f4c(A[i], q), f4c(B[j], q), acc[i][j]);
 #define FAT_STAGE(BUF, LAST_A, LAST_B, FREE_A, FREE_B)                                                           \
     {                                                                                                            \
-        FSTAMP(ft0)                                                                                              \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                          \
-            if (fetching && (q % FAT_DG) == 0) { FAT_DMA_ROWS((BUF) ^ 1, 2 * q, 2 * q + 2 * FAT_DG) }   /* the next stage, into the buffer the previous barrier released */ \
+            if (fetching) { FAT_DMA_ROWS((BUF) ^ 1, 2 * q, 2 * q + 2) }   /* 4 of the next stage's 16 DMA requests, into the buffer the previous barrier released */ \
             __builtin_amdgcn_sched_barrier(0);                                                                   \
             FAT_Q(fa0, fb0, q)                                                                                   \
             __builtin_amdgcn_sched_barrier(0);                                                                   \
         }                                                                                                        \
         if (fetching) FAT_DMA_NEXT()                                                                             \
-        FSTAMP(ft1)                                                                                              \
         mfma_block<4, 4>(acc, fa1, fb1);                                                                         \
         mfma_block<4, 4>(acc, fa2, fb2);                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        FSTAMP(ft2)                                                                                              \
         /* this wave's LDS-DMA of the next stage must have LANDED before the barrier lets the other waves read it: an       \
            explicit vmcnt(0) (gfx9 encoding, expcnt 7 = no wait) -- the compiler's fence only covers this wave's own reads */ \
         __builtin_amdgcn_s_waitcnt(0x0070);                                                                      \
         __syncthreads();   /* every wave holds the rest of BUF in registers */                                   \
-        FSTAMP(ft3)                                                                                              \
-        {   /* k-block 3 with the next stage's 32 LDS reads in groups of FAT_RG between its MFMAs.  (Behind the very last  \
+        {   /* k-block 3 with the next stage's 32 LDS reads in groups of 4 between its MFMAs.  (Behind the very last \
                stage the reads fetch stale LDS contents that nobody uses: no branch around MFMAs.) */            \
             const float4 *sp = SP((BUF) ^ 1), *sq = SQ((BUF) ^ 1);                                               \
             FAT_READ(sp, sq, 0, fa0, fb0)                                                                        \
@@ -1093,14 +1029,12 @@ __global__ __launch_bounds__(256, 1) void gemm_fat_kernel(GemmArgs a) {
             FAT_READ(sp, sq, 2, fa2, fb2)                                                                        \
             FAT_READ(sp, sq, 3, FREE_A, FREE_B)                                                                  \
             mfma_block<4, 4>(acc, LAST_A, LAST_B);                                                               \
-            _Pragma("unroll") for (int m = 0; m < 32 / FAT_RG; ++m) {                                            \
-                __builtin_amdgcn_sched_group_barrier(0x100, FAT_RG, 0);                                          \
-                __builtin_amdgcn_sched_group_barrier(0x008, 2 * FAT_RG, 0);                                      \
+            _Pragma("unroll") for (int m = 0; m < 8; ++m) {                                                      \
+                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                               \
+                __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);                                               \
             }                                                                                                    \
         }                                                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        FSTAMP(ft4)                                                                                              \
-        FSTAMP_SUM()                                                                                             \
     }
     for (;;) {
         for (int st = 0; st < nstage; st += 2) {
@@ -1134,29 +1068,15 @@ __global__ __launch_bounds__(256, 1) void gemm_fat_kernel(GemmArgs a) {
                         }
                         *reinterpret_cast<float4 *>(dbase + ((int64_t)(i * 8 + 2 * g) * a.ldd + j * 32) * 16 + dlane) = make_float4(v[0], v[1], v[2], v[3]);
                     }
-#ifndef SDFA_FAT_NOZERO   /* timing experiment: what zero-start accumulators could save at most -- the 256 register
-                             writes per tile simply left out (wrong results from the second tile of a workgroup on) */
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#endif
                 }
             }
         }
-#ifdef SDFA_STAMPS
-        { unsigned long long te; FSTAMP(te) fs_epi += te - ft4; ++fs_tiles; }
-#endif
         advance(t);
         if (!live(t)) break;
     }
-#ifdef SDFA_STAMPS
-    if (lane == 0 && nstage <= 16) {
-        atomicAdd(&g_stamp[0], fs_k0); atomicAdd(&g_stamp[1], fs_k12); atomicAdd(&g_stamp[2], fs_bar); atomicAdd(&g_stamp[3], fs_last);
-        atomicAdd(&g_stamp[4], fs_n); atomicAdd(&g_stamp[5], fs_epi); atomicAdd(&g_stamp[6], fs_tiles);
-    }
-#endif
 #undef FAT_STAGE
-#undef FAT_RG
-#undef FAT_DG
 #undef FAT_Q
 #undef FAT_DMA_ROWS
 #undef FAT_DMA_NEXT
@@ -1177,14 +1097,6 @@ hipError_t launch_fat(const GemmArgs &a, hipStream_t s) {
 }
 
 }  // namespace
-
-#ifdef SDFA_STAMPS
-extern "C" int sdfa_debug_read_stamps(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 8) != hipSuccess) return -3;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof z) != hipSuccess) return -3; }
-    return 0;
-}
-#endif
 
 // "gemm_variant" option (sdfa_debug_set_option, thread-local): 0 = default choice per shape -- gemm_fat_kernel where its 256 x 256
 // tiles fill the chip at least twice, else the LDS-tiled 128 x 128 kernel (256 x 256 gemm_big_kernel for the 8192-deep frequency

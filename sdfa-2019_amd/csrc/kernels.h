@@ -10,14 +10,11 @@ int sdfa_failv(int code, const char *fmt, va_list ap);
 
 enum { ACT_NONE = 0, ACT_LRELU = 1, ACT_TANH = 2 };
 
-// Frequency-LSTM hidden states are stored tile-major: float4[column block of 128][HF_SLAB_ROWS][128], of which the
-// first 8192/4 = 2048 rows of a slab are used.  The pad rows keep the slab stride off a power of two: every workgroup
-// of the projection GEMM streams its own slab front to back at about the same pace, and with a 4 MiB stride all of
-// them would sit on the same HBM channels at the same time.
-#ifndef SDFA_HF_PAD
-#define SDFA_HF_PAD 0
-#endif
-constexpr int HF_SLAB_ROWS = 2048 + SDFA_HF_PAD;
+// Frequency-LSTM hidden states are stored tile-major: float4[column block of 128][HF_SLAB_ROWS][128], 8192/4 = 2048 rows
+// per slab with no padding, so the slab stride (4 MiB) is a power of two.  Padding it off a power of two, so that the
+// projection GEMM's workgroups would not all stream the same HBM channels at once, measured no difference
+// (profiles/HISTORY.md, layout experiments on the hidden states).
+constexpr int HF_SLAB_ROWS = 2048;
 enum { OUT_K4 = 0, OUT_ROW = 1 };
 constexpr int SDFA_MAX_DESTS = 8;   // output destinations of the regressor epilogues: the local buffer + up to 7 peers
 

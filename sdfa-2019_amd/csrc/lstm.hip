@@ -17,16 +17,6 @@
 #include "common.h"
 #include "kernels.h"
 
-#ifdef SDFA_STAMPS
-__device__ unsigned long long g_lstamp[8];
-__device__ unsigned long long g_lspan[4] = {~0ull, 0ull, 0ull, 0ull};
-__device__ unsigned long long g_lsub[4];     // cell-update sub-phases: x DMA issue, columns 0-31, columns 32-63
-__device__ unsigned long long g_lxcd[8][4];   // per XCD (block id % 8): max end, sum of lifetimes, count, last start   // min start, max end, sum of lifetimes (100 MHz ticks), sum of lifetimes (shader cycles)
-#define LSTAMP(t) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#else
-#define LSTAMP(t)
-#endif
-
 namespace {
 
 // fp32 MFMA and the vector ALU do NOT overlap on this chip -- neither across the waves of a SIMD nor inside one wave
@@ -75,21 +65,6 @@ __device__ __forceinline__ void lstm_cell_quad(const f32x16 &ai, const f32x16 &a
     for (int p = 0; p < 2; ++p) {
         const int r = 4 * g + 2 * p;
         f32x2 cp = {c[r], c[r + 1]};
-#ifdef SDFA_FAKE_CELL   /* timing experiment only: what does the cell math cost? */
-        { const f32x2 cn = f32x2{af[r], af[r + 1]} * cp + f32x2{ai[r], ai[r + 1]} * f32x2{ag[r], ag[r + 1]}; c[r] = cn.x; c[r + 1] = cn.y; hv[p] = f32x2{ao[r], ao[r + 1]} * cn; continue; }
-#endif
-#ifdef SDFA_OLD_CELL   /* A/B build only (make EXP=OLD_CELL): round 3's cell update on unscaled weights */
-        if (FREQ) {
-            const f32x2 ig = sigmoid2(f32x2{ai[r], ai[r + 1]}), fg = sigmoid2(f32x2{af[r], af[r + 1]});
-            const f32x2 fc = fg * cp;
-            const f32x2 gg = __builtin_elementwise_fma(rcp2(exp2n(f32x2{ag[r], ag[r + 1]} * 2.8853900817779268f) + 1.0f), f32x2{2.0f, 2.0f}, f32x2{-1.0f, -1.0f});
-            const f32x2 cn = __builtin_elementwise_fma(ig, gg, fc);
-            c[r] = cn.x; c[r + 1] = cn.y;
-            const f32x2 eo = exp2n(f32x2{ao[r], ao[r + 1]} * 1.4426950408889634f), ec = exp2n(cn * 2.8853900817779268f);
-            hv[p] = (1.0f - ec) * rcp2((1.0f + eo) * (1.0f + ec));
-            continue;
-        }
-#endif
         if (FREQ) {
             // Round 4: the accumulators arrive as exponents of two (the host folds log2 e / 2 log2 e into the weights and the bias:
             // api.cpp), and the cell state is kept in the same units, c~ = 2 log2 e * c (it never leaves the kernel) -- so no gate and
@@ -140,7 +115,7 @@ __device__ __forceinline__ void lstm_cell_quad(const f32x16 &ai, const f32x16 &a
 //
 // PERSIST (option freq_lstm_shape=5): the grid is two workgroups per CU and every workgroup takes (direction, column tile)
 // pairs from a queue head in the workspace until the queue is empty, instead of one hardware-dispatched workgroup per
-// pair.  Built because the stamps (tools/stamp_lstm2.py) show a CU slot empty 2.5-3 % of a launch between the end of one
+// pair.  Built because phase stamps (profiles/HISTORY.md) showed a CU slot empty 2.5-3 % of a launch between the end of one
 // 1.5 ms workgroup and the start of the next, plus +-2 % between XCDs under the static block-id -> XCD partition.
 // Bit-identical.  With the scalar cell update it measured 2.4-3.4 % SLOWER than hardware dispatch (48.3 -> 49.4 ms per 8192
 // frames), with the packed one 0.5 % faster (and hardware dispatch 2.5 % slower): how two starving partners interleave is
@@ -219,21 +194,17 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
     // one k-block: 32 MFMAs, component-major (consecutive MFMAs go to different accumulators)
 #define FV_MFMA(W0, W1, W2, W3, B0, B1)                                                                      \
     _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                          \
-        acc[0][0] = MFMA(SDFA_OP(f4c(W0, q)), SDFA_OP(f4c(B0, q)), acc[0][0]);                               \
-        acc[0][1] = MFMA(SDFA_OP(f4c(W0, q)), SDFA_OP(f4c(B1, q)), acc[0][1]);                               \
-        acc[1][0] = MFMA(SDFA_OP(f4c(W1, q)), SDFA_OP(f4c(B0, q)), acc[1][0]);                               \
-        acc[1][1] = MFMA(SDFA_OP(f4c(W1, q)), SDFA_OP(f4c(B1, q)), acc[1][1]);                               \
-        acc[2][0] = MFMA(SDFA_OP(f4c(W2, q)), SDFA_OP(f4c(B0, q)), acc[2][0]);                               \
-        acc[2][1] = MFMA(SDFA_OP(f4c(W2, q)), SDFA_OP(f4c(B1, q)), acc[2][1]);                               \
-        acc[3][0] = MFMA(SDFA_OP(f4c(W3, q)), SDFA_OP(f4c(B0, q)), acc[3][0]);                               \
-        acc[3][1] = MFMA(SDFA_OP(f4c(W3, q)), SDFA_OP(f4c(B1, q)), acc[3][1]);                               \
+        acc[0][0] = MFMA(f4c(W0, q), f4c(B0, q), acc[0][0]);                                                 \
+        acc[0][1] = MFMA(f4c(W0, q), f4c(B1, q), acc[0][1]);                                                 \
+        acc[1][0] = MFMA(f4c(W1, q), f4c(B0, q), acc[1][0]);                                                 \
+        acc[1][1] = MFMA(f4c(W1, q), f4c(B1, q), acc[1][1]);                                                 \
+        acc[2][0] = MFMA(f4c(W2, q), f4c(B0, q), acc[2][0]);                                                 \
+        acc[2][1] = MFMA(f4c(W2, q), f4c(B1, q), acc[2][1]);                                                 \
+        acc[3][0] = MFMA(f4c(W3, q), f4c(B0, q), acc[3][0]);                                                 \
+        acc[3][1] = MFMA(f4c(W3, q), f4c(B1, q), acc[3][1]);                                                 \
     }
     float4 wn0, wn1, wn2, wn3;
     FV_WLOAD(0, wn0, wn1, wn2, wn3)
-#ifdef SDFA_STAMPS
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t3a = 0, t3b = 0, t3c = 0, t4 = 0, t5 = 0, v_init = 0, v_k = 0, v_b1 = 0, v_ep = 0, v_b2 = 0, v_e0 = 0, v_e1 = 0, v_e2 = 0;
-    const unsigned long long life_r0 = wall_clock64(), life_c0 = clock64();
-#endif
     __syncthreads();   // bias and the first x tile are in LDS (the fence drains the DMA)
 
     for (int s = 0; s < 32; ++s) {
@@ -246,7 +217,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
         // full s_waitcnt at the end of every K iteration, or spilled 253 registers.
         float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba0, ba1, bb0, bb1;
         f32x16 acc[4][NJ];
-        LSTAMP(t0)
 #pragma unroll
         for (int gt = 0; gt < 4; ++gt)
 #pragma unroll
@@ -260,14 +230,7 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
             }
         const int nkb = s > 0 ? 24 : 8;        // h_{-1} = 0: the first step contracts x_f only
         FV_BLOAD(0, ba0, ba1)
-#ifndef SDFA_PRIO_MFMA
-#define SDFA_PRIO_MFMA 1
-#endif
-#ifndef SDFA_PRIO_EPI
-#define SDFA_PRIO_EPI 0
-#endif
-        __builtin_amdgcn_s_setprio(SDFA_PRIO_MFMA);
-        LSTAMP(t1)
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll 1
         for (int kb = 0; kb < nkb; kb += 2) {
             FV_WLOAD(kb + 1, wb0, wb1, wb2, wb3)
@@ -283,17 +246,11 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
             __builtin_amdgcn_sched_barrier(0);
         }
         FV_WLOAD(0, wn0, wn1, wn2, wn3)     // k-block 0 for the NEXT step: in flight during the cell update (weights do not change)
-        __builtin_amdgcn_s_setprio(SDFA_PRIO_EPI);
-#ifdef SDFA_STAMPS
-        asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][1]), "v"(acc[1][1]), "v"(acc[2][1]), "v"(acc[3][1]));   // all MFMAs done
-#endif
-        LSTAMP(t2)
+        __builtin_amdgcn_s_setprio(0);
         // every wave has finished reading sH / sX[cur] (all LDS reads were consumed by MFMAs, the wrap-around one is waited
         // for here); the weight request in flight is not waited for
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        LSTAMP(t3)
         if (s + 1 < 32) { XDMA(dir ? 30 - s : s + 1, cur ^ 1) }   // lands during the cell update; sX[cur ^ 1] was last read in step s - 1
-        LSTAMP(t3a)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
 #pragma unroll
@@ -304,9 +261,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
                 sH[hq_idx][j * 32 + l31] = hq;
                 HF[((m0 >> 7) * (int64_t)HF_SLAB_ROWS + (f * 64 + dir * 32 + hq_idx)) * 128 + (m0 & 127) + j * 32 + l31] = hq;
             }
-#ifdef SDFA_STAMPS
-            if (j == 0) LSTAMP(t3b) else LSTAMP(t3c)
-#endif
         }
         // h_s and the next x tile must be in LDS before anyone starts step s+1: this wave's LDS writes (lgkmcnt) and its four
         // DMA requests.  Vector-memory operations of a wave complete in issue order on gfx9-family parts (one in-order
@@ -316,26 +270,8 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
         // (the builtin wait is the same instruction again: the compiler's own waitcnt bookkeeping does not look inside asm
         // and would otherwise put a full vmcnt(0) in front of the next LDS read -- inside the K loop -- for the DMA's sake)
         __builtin_amdgcn_s_waitcnt(0x0078);     // gfx9 encoding: vmcnt = 8, expcnt = 7 (no wait), lgkmcnt = 0
-        LSTAMP(t4)
         asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef SDFA_STAMPS
-        LSTAMP(t5)
-        if (s > 0) { v_init += t1 - t0; v_k += t2 - t1; v_b1 += t3 - t2; v_ep += t4 - t3; v_b2 += t5 - t4; v_e0 += t3a - t3; v_e1 += t3b - t3a; v_e2 += t3c - t3b; }
-#endif
     }
-#ifdef SDFA_STAMPS
-    if (lane == 0) {
-        atomicAdd(&g_lstamp[0], v_init); atomicAdd(&g_lstamp[1], v_k); atomicAdd(&g_lstamp[2], v_b1); atomicAdd(&g_lstamp[3], v_ep);
-        atomicAdd(&g_lstamp[4], v_b2); atomicAdd(&g_lstamp[6], 31ull);
-        atomicAdd(&g_lsub[0], v_e0); atomicAdd(&g_lsub[1], v_e1); atomicAdd(&g_lsub[2], v_e2);
-        if (wave == 0) {
-            const unsigned long long r1 = wall_clock64();
-            atomicMin(&g_lspan[0], life_r0); atomicMax(&g_lspan[1], r1);
-            atomicAdd(&g_lspan[2], r1 - life_r0); atomicAdd(&g_lspan[3], (unsigned long long)clock64() - life_c0);
-            atomicMax(&g_lxcd[blockIdx.x & 7][0], r1); atomicAdd(&g_lxcd[blockIdx.x & 7][1], r1 - life_r0); atomicAdd(&g_lxcd[blockIdx.x & 7][2], 1ull); atomicMax(&g_lxcd[blockIdx.x & 7][3], life_r0);
-        }
-    }
-#endif
     if (!PERSIST) break;
   }
 #undef XDMA
@@ -416,27 +352,27 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
 #define F3_SB() __builtin_amdgcn_sched_barrier(0);
 #define F3_Q(W0, W1, W2, W3, B0, B1, q)                                                                      \
     {                                                                                                        \
-        acc[0][0] = MFMA(SDFA_OP(f4c(W0, q)), SDFA_OP(f4c(B0, q)), acc[0][0]);                               \
-        acc[0][1] = MFMA(SDFA_OP(f4c(W0, q)), SDFA_OP(f4c(B1, q)), acc[0][1]);                               \
-        acc[1][0] = MFMA(SDFA_OP(f4c(W1, q)), SDFA_OP(f4c(B0, q)), acc[1][0]);                               \
-        acc[1][1] = MFMA(SDFA_OP(f4c(W1, q)), SDFA_OP(f4c(B1, q)), acc[1][1]);                               \
-        acc[2][0] = MFMA(SDFA_OP(f4c(W2, q)), SDFA_OP(f4c(B0, q)), acc[2][0]);                               \
-        acc[2][1] = MFMA(SDFA_OP(f4c(W2, q)), SDFA_OP(f4c(B1, q)), acc[2][1]);                               \
-        acc[3][0] = MFMA(SDFA_OP(f4c(W3, q)), SDFA_OP(f4c(B0, q)), acc[3][0]);                               \
-        acc[3][1] = MFMA(SDFA_OP(f4c(W3, q)), SDFA_OP(f4c(B1, q)), acc[3][1]);                               \
+        acc[0][0] = MFMA(f4c(W0, q), f4c(B0, q), acc[0][0]);                                                 \
+        acc[0][1] = MFMA(f4c(W0, q), f4c(B1, q), acc[0][1]);                                                 \
+        acc[1][0] = MFMA(f4c(W1, q), f4c(B0, q), acc[1][0]);                                                 \
+        acc[1][1] = MFMA(f4c(W1, q), f4c(B1, q), acc[1][1]);                                                 \
+        acc[2][0] = MFMA(f4c(W2, q), f4c(B0, q), acc[2][0]);                                                 \
+        acc[2][1] = MFMA(f4c(W2, q), f4c(B1, q), acc[2][1]);                                                 \
+        acc[3][0] = MFMA(f4c(W3, q), f4c(B0, q), acc[3][0]);                                                 \
+        acc[3][1] = MFMA(f4c(W3, q), f4c(B1, q), acc[3][1]);                                                 \
     }
     // the step's very first MFMA group: column tile 1 starts from tile 0's seeds (C = acc[gt][0], D = acc[gt][1]) BEFORE tile 0's own
     // first product overwrites them in place -- same sums as seeding both (bitwise)
 #define F3_QSEED(W0, W1, W2, W3, B0, B1)                                                                     \
     {                                                                                                        \
-        acc[0][1] = MFMA(SDFA_OP(f4c(W0, 0)), SDFA_OP(f4c(B1, 0)), acc[0][0]);                               \
-        acc[0][0] = MFMA(SDFA_OP(f4c(W0, 0)), SDFA_OP(f4c(B0, 0)), acc[0][0]);                               \
-        acc[1][1] = MFMA(SDFA_OP(f4c(W1, 0)), SDFA_OP(f4c(B1, 0)), acc[1][0]);                               \
-        acc[1][0] = MFMA(SDFA_OP(f4c(W1, 0)), SDFA_OP(f4c(B0, 0)), acc[1][0]);                               \
-        acc[2][1] = MFMA(SDFA_OP(f4c(W2, 0)), SDFA_OP(f4c(B1, 0)), acc[2][0]);                               \
-        acc[2][0] = MFMA(SDFA_OP(f4c(W2, 0)), SDFA_OP(f4c(B0, 0)), acc[2][0]);                               \
-        acc[3][1] = MFMA(SDFA_OP(f4c(W3, 0)), SDFA_OP(f4c(B1, 0)), acc[3][0]);                               \
-        acc[3][0] = MFMA(SDFA_OP(f4c(W3, 0)), SDFA_OP(f4c(B0, 0)), acc[3][0]);                               \
+        acc[0][1] = MFMA(f4c(W0, 0), f4c(B1, 0), acc[0][0]);                                                 \
+        acc[0][0] = MFMA(f4c(W0, 0), f4c(B0, 0), acc[0][0]);                                                 \
+        acc[1][1] = MFMA(f4c(W1, 0), f4c(B1, 0), acc[1][0]);                                                 \
+        acc[1][0] = MFMA(f4c(W1, 0), f4c(B0, 0), acc[1][0]);                                                 \
+        acc[2][1] = MFMA(f4c(W2, 0), f4c(B1, 0), acc[2][0]);                                                 \
+        acc[2][0] = MFMA(f4c(W2, 0), f4c(B0, 0), acc[2][0]);                                                 \
+        acc[3][1] = MFMA(f4c(W3, 0), f4c(B1, 0), acc[3][0]);                                                 \
+        acc[3][0] = MFMA(f4c(W3, 0), f4c(B0, 0), acc[3][0]);                                                 \
     }
     // one k-block on the operand set C* while the set N* is refilled for the next one: weights at scalar offset `so`,
     // operand rows at `bp` (per-lane pointer to the row pair of the next k-block).  F3_KB_SEED: the step's first k-block
@@ -463,7 +399,7 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
         F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 3)                                                                \
     }
     // the last k-block of a step: the same, with the four LDS-DMA requests of the next x tile behind its last two MFMA
-    // groups -- an LDS-DMA request takes ~100 cycles to issue (tools/stamp_fat.py), four in a row in front of the cell update
+    // groups -- an LDS-DMA request takes ~100 cycles to issue (profiles/HISTORY.md), four in a row in front of the cell update
     // cost 400; here most of that rides in the MFMAs' shadow.  They come AFTER this k-block's weight requests, so the next
     // step's first weight wait (loads return in issue order) does not include the tile's HBM round trip.
 #define F3_KB_LAST(CW0, CW1, CW2, CW3, CB0, CB1, NW0, NW1, NW2, NW3, NB0, NB1, so, bp, dma, fnext, par)      \
@@ -488,16 +424,12 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
                                          (void __attribute__((address_space(3))) *)(&sXH[par][4 * i + wave][0]), 16, 0, 0);
     float4 wa0, wa1, wa2, wa3, wb0, wb1, wb2, wb3, ba0, ba1, bb0, bb1;
     wa0 = F3_W(0u, 0); wa1 = F3_W(0u, 1); wa2 = F3_W(0u, 2); wa3 = F3_W(0u, 3);
-#ifdef SDFA_STAMPS
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, v_init = 0, v_k = 0, v_ep = 0, v_b2 = 0;
-#endif
     __syncthreads();   // bias and the first x tile are in LDS (the fence drains the DMA)
 
     for (int s = 0; s < 32; ++s) {
         const int f = dir ? 31 - s : s;
         const int cur = s & 1;
         f32x16 acc[4][NJ];
-        LSTAMP(t0)
         // the first k-block's operand rows FIRST (LDS answers a wave's reads in order): the step's first MFMA then waits for these two and
         // its own four seed quads, the later seeds land under the MFMAs in front of them
         const float4 *brow = &sXH[cur][h][l31];                 // row pair of k-block kb: brow + kb * 2 * BT
@@ -516,7 +448,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
                 acc[gt][0][4 * g + 2] = b.z; acc[gt][0][4 * g + 3] = b.w;
             }
         const int trips = s > 0 ? 3 : 1;       // h_{-1} = 0: the first step contracts x_f only (8 of the 24 k-blocks)
-        LSTAMP(t1)
         // a trip = 8 k-blocks.  Trip 0 is written out in front of the loop: its first MFMA group is the seeded one, and as straight-line code
         // the compiler sees that (a run-time `t == 0` inside the loop made it copy the 128 accumulator registers of tile 1 around the branch)
 #define F3_TRIP(FIRST_KB, t_)                                                                                                     \
@@ -539,14 +470,10 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
         for (int t = 1; t < trips; ++t) F3_TRIP(F3_KB, t)
 #undef F3_TRIP
         F3_SB()
-#ifdef SDFA_STAMPS
-        asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][1]), "v"(acc[1][1]), "v"(acc[2][1]), "v"(acc[3][1]));   // all MFMAs done
-#endif
-        LSTAMP(t2)
         // The next x tile: four plain 16-byte loads per lane into registers, requested here -- BEHIND the step's last weight
         // requests, so that no weight wait includes their HBM round trip (loads return in issue order) -- and written to the
         // OTHER parity's buffer after the cell update, which covers the round trip.  (An LDS-DMA request for these rows, 8 MB
-        // apart, took ~230 cycles to ISSUE: 930 per step, wherever it was placed; tools/stamp_lstm2.py.)  wa* now hold
+        // apart, took ~230 cycles to ISSUE: 930 per step, wherever it was placed; profiles/HISTORY.md.)  wa* now hold
         // k-block 0 of the next step's weights.
         float4 xr0, xr1, xr2, xr3;
         {
@@ -567,18 +494,8 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
         sXH[cur ^ 1][wave][lane] = xr0; sXH[cur ^ 1][4 + wave][lane] = xr1; sXH[cur ^ 1][8 + wave][lane] = xr2; sXH[cur ^ 1][12 + wave][lane] = xr3;
         // h_s and the next x tile must be in LDS before anyone starts step s+1: this wave's LDS writes (lgkmcnt); the
         // hidden-state stores need not be acknowledged (a bare barrier: __syncthreads() would add their vmcnt(0))
-        LSTAMP(t3)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef SDFA_STAMPS
-        LSTAMP(t4)
-        if (s > 0) { v_init += t1 - t0; v_k += t2 - t1; v_ep += t3 - t2; v_b2 += t4 - t3; }
-#endif
     }
-#ifdef SDFA_STAMPS
-    if (lane == 0) {
-        atomicAdd(&g_lstamp[0], v_init); atomicAdd(&g_lstamp[1], v_k); atomicAdd(&g_lstamp[3], v_ep); atomicAdd(&g_lstamp[4], v_b2); atomicAdd(&g_lstamp[6], 31ull);
-    }
-#endif
 #undef XDMA3
 #undef XDMA3_HALF
 #undef F3_KB_LAST
@@ -931,15 +848,11 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16p_v3_kernel(FreqLstmArgs
 #pragma unroll
         for (int r = 0; r < 16; ++r) c[j][r] = 0.f;
     __syncthreads();   // bias and the first x tile are in LDS
-#ifdef SDFA_STAMPS
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, v_init = 0, v_k = 0, v_ep = 0, v_b2 = 0;
-#endif
 
     for (int s = 0; s < 32; ++s) {
         const int f = dir ? 31 - s : s;
         const int cur = s & 1;
         f32x16 acc[4][2];
-        LSTAMP(t0)
         // k-step 0's operand planes first, then the seeds (the bias) of column tile 0 only: freq_lstm_v3_kernel has the reasons
         const int trips = s > 0 ? 3 : 1;       // h_{-1} = 0: the first step contracts x_f only (4 of the 12 k-steps)
         const bf16x8 *brow = P6_ROW(cur, 0, h) + l31;            // operand rows of k-step ks: brow + ks * 2 * BT (+ plane * ROWS * BT, + 32 for the second column tile)
@@ -956,7 +869,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16p_v3_kernel(FreqLstmArgs
                 acc[gt][0][4 * g + 0] = b.x; acc[gt][0][4 * g + 1] = b.y;
                 acc[gt][0][4 * g + 2] = b.z; acc[gt][0][4 * g + 3] = b.w;
             }
-        LSTAMP(t1)
         // a trip = 4 k-steps; trip 0, with the seeded first group, is written out in front of the loop (straight-line code: exact LDS waits)
 #define P6_TRIP(KS6_FIRST, KS3_FIRST, t_)                                                                                         \
         {                                                                                                                         \
@@ -981,10 +893,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16p_v3_kernel(FreqLstmArgs
         for (int t = 1; t < trips; ++t) P6_TRIP(P6_KS, P3_KS, t)
 #undef P6_TRIP
         P6_SB()
-#ifdef SDFA_STAMPS
-        asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][1]), "v"(acc[1][1]), "v"(acc[2][1]), "v"(acc[3][1]));   // all MFMAs done
-#endif
-        LSTAMP(t2)
         // the next x tile: requested BEHIND the step's last weight requests (loads return in issue order), split and written to the
         // other parity after the cell update, which covers the round trip
         P6_XLOAD(s + 1 < 32 ? (dir ? 30 - s : s + 1) : f)
@@ -1000,19 +908,9 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16p_v3_kernel(FreqLstmArgs
             for (int q = 0; q < 2; ++q) P6_SPLIT_STORE(cur ^ 1, 8 + 4 * wave + 2 * q + h, j * 32 + l31, hq[2 * q], hq[2 * q + 1])
         }
         P6_XSTORE(cur ^ 1)
-        LSTAMP(t3)
         // h_s and the next x tile must be in LDS before anyone starts step s+1 (the hidden-state stores need not be acknowledged)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef SDFA_STAMPS
-        LSTAMP(t4)
-        if (s > 0) { v_init += t1 - t0; v_k += t2 - t1; v_ep += t3 - t2; v_b2 += t4 - t3; }
-#endif
     }
-#ifdef SDFA_STAMPS
-    if (lane == 0) {
-        atomicAdd(&g_lstamp[0], v_init); atomicAdd(&g_lstamp[1], v_k); atomicAdd(&g_lstamp[3], v_ep); atomicAdd(&g_lstamp[4], v_b2); atomicAdd(&g_lstamp[6], 31ull);
-    }
-#endif
     if (!PERSIST) break;
   }
 #undef P6_ROW
@@ -1239,21 +1137,12 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) ucol[j] = cmap[(int64_t)(dir ? 62 : 1) * a.Nc + j * 32];
     }
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)   /* (the host pass of a __device__ template rejects the asm constraints) */
-#define TSTAMP(t) LSTAMP(t)
-#else
-#define TSTAMP(t)
-#endif
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-    unsigned long long tt0 = 0, tt1 = 0, tt2 = 0, tt3 = 0, tv_k = 0, tv_cell = 0, tv_bar = 0;
-#endif
     for (int s = 0; s < 64; ++s) {
         const int t = dir ? 63 - s : s;
         const int tn = dir ? t - 1 : t + 1;
         const int64_t tcol = (int64_t)t * a.Nc;
         const float4 *sHc = sHt + (size_t)(s & 1) * 64 * BT;
         float4 *sHn = sHt + (size_t)((s & 1) ^ 1) * 64 * BT;
-        TSTAMP(tt0)
 
         if (s > 0) {
             float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba[NT], bb[NT];
@@ -1261,10 +1150,10 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
             // one or two at a time in front of the four MFMA groups of a k-block (freq_lstm_v3_kernel)
 #define TL_SB() __builtin_amdgcn_sched_barrier(0);
 #define TL_Q(W0, W1, W2, W3, B, q)                                                                               \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[0][j] = MFMA(SDFA_OP(f4c(W0, q)), SDFA_OP(f4c(B[j], q)), acc[0][j]); \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[1][j] = MFMA(SDFA_OP(f4c(W1, q)), SDFA_OP(f4c(B[j], q)), acc[1][j]); \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[2][j] = MFMA(SDFA_OP(f4c(W2, q)), SDFA_OP(f4c(B[j], q)), acc[2][j]); \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[3][j] = MFMA(SDFA_OP(f4c(W3, q)), SDFA_OP(f4c(B[j], q)), acc[3][j]);
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[0][j] = MFMA(f4c(W0, q), f4c(B[j], q), acc[0][j]);        \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[1][j] = MFMA(f4c(W1, q), f4c(B[j], q), acc[1][j]);        \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[2][j] = MFMA(f4c(W2, q), f4c(B[j], q), acc[2][j]);        \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[3][j] = MFMA(f4c(W3, q), f4c(B[j], q), acc[3][j]);
 #define TL_KB(CW0, CW1, CW2, CW3, CB, NW0, NW1, NW2, NW3, NB, so, bp)                                            \
     {                                                                                                            \
         TL_SB() NW0 = TL_W1(so, 0); NW1 = TL_W1(so, 1); TL_SB()                                                  \
@@ -1300,10 +1189,6 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
 #undef TL_SB
             wn0 = wa0; wn1 = wa1; wn2 = wa2; wn3 = wa3;      // k-block 0 again: the next step's first operands
         }
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-        if (NT == 2) asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][NT - 1]), "v"(acc[1][NT - 1]), "v"(acc[2][NT - 1]), "v"(acc[3][NT - 1]));   // all MFMAs done
-#endif
-        TSTAMP(tt1)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -1326,18 +1211,9 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) ucol[j] = cmap[(int64_t)t2 * a.Nc + j * 32];
         }
-        TSTAMP(tt2)
         __syncthreads();   // h_s complete in sHn before anyone reads it; sHc free for step s+1's writes
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-        TSTAMP(tt3)
-        if (s > 0) { tv_k += tt1 - tt0; tv_cell += tt2 - tt1; tv_bar += tt3 - tt2; }
-#endif
     }
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-    if (NT == 2 && lane == 0) { atomicAdd(&g_lsub[0], tv_k); atomicAdd(&g_lsub[1], tv_cell); atomicAdd(&g_lsub[2], tv_bar); atomicAdd(&g_lsub[3], 63ull); }
-#endif
 #undef TL_GX
-#undef TSTAMP
 #undef TL_LOAD
 #undef TL_W1
 }
@@ -1473,10 +1349,10 @@ __global__ __launch_bounds__(512 / G) void time_lstm_split_kernel(TimeLstmArgs a
             float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba, bb;
 #define TS_SB() __builtin_amdgcn_sched_barrier(0);
 #define TS_Q(W0, W1, W2, W3, B, q)                                              \
-    acc[0][0] = MFMA(SDFA_OP(f4c(W0, q)), SDFA_OP(f4c(B, q)), acc[0][0]);       \
-    acc[1][0] = MFMA(SDFA_OP(f4c(W1, q)), SDFA_OP(f4c(B, q)), acc[1][0]);       \
-    acc[2][0] = MFMA(SDFA_OP(f4c(W2, q)), SDFA_OP(f4c(B, q)), acc[2][0]);       \
-    acc[3][0] = MFMA(SDFA_OP(f4c(W3, q)), SDFA_OP(f4c(B, q)), acc[3][0]);
+    acc[0][0] = MFMA(f4c(W0, q), f4c(B, q), acc[0][0]);                         \
+    acc[1][0] = MFMA(f4c(W1, q), f4c(B, q), acc[1][0]);                         \
+    acc[2][0] = MFMA(f4c(W2, q), f4c(B, q), acc[2][0]);                         \
+    acc[3][0] = MFMA(f4c(W3, q), f4c(B, q), acc[3][0]);
 #define TS_KB(CW0, CW1, CW2, CW3, CB, NW0, NW1, NW2, NW3, NB, so, bp)           \
     {                                                                           \
         TS_SB() NW0 = TS_W1(so, 0); NW1 = TS_W1(so, 1); TS_SB()                 \
@@ -1677,7 +1553,7 @@ __global__ __launch_bounds__(256) void time_lstm_split16_kernel(TimeLstmArgs a, 
                 __builtin_amdgcn_sched_barrier(0);                                                                  \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                        \
                     _Pragma("unroll") for (int tl = 0; tl < 8; ++tl)                                                 \
-                        acc[tl >> 1][tl & 1] = MFMA16(SDFA_OP(f4c(WC[tl], j)), SDFA_OP(f4c(BC, j)), acc[tl >> 1][tl & 1]); \
+                        acc[tl >> 1][tl & 1] = MFMA16(f4c(WC[tl], j), f4c(BC, j), acc[tl >> 1][tl & 1]);             \
             }
 #pragma unroll 1
             for (int K16 = 0; K16 < 16; K16 += 2) {
@@ -1810,18 +1686,11 @@ __global__ __launch_bounds__(512, 2) void time_lstm_bf16_kernel(TimeLstmArgs a) 
         for (int gt = 0; gt < 4; ++gt) { S[gt] = TB_W(2, 0, gt); R[gt] = TB_W(1, 0, gt); H6a[gt] = TB_W(0, 0, gt); }
     }
 
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)    /* diagnostic build: K loop / cell update + plane split / barrier, as time_lstm_body */
-    unsigned long long bt0 = 0, bt1 = 0, bt2 = 0, bt3 = 0, bv_k = 0, bv_cell = 0, bv_bar = 0;
-#define BSTAMP(t) LSTAMP(t)
-#else
-#define BSTAMP(t)
-#endif
     for (int s = 0; s < 64; ++s) {
         const int t = dir ? 63 - s : s;
         const int tn = dir ? t - 1 : t + 1;
         const int64_t mcol = (int64_t)t * a.Nc + n0 + l31;
         const int cur = s & 1;
-        BSTAMP(bt0)
 
         if (X6 && s > 0) {
             // six products per k-step and accumulator, smallest first: lo*hi, mid*mid, mid*hi, hi*lo, hi*mid, hi*hi (NT = 1: four
@@ -1915,10 +1784,6 @@ __global__ __launch_bounds__(512, 2) void time_lstm_bf16_kernel(TimeLstmArgs a) 
 #undef TB_HH
 #undef TB_SB
         }
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][NT - 1]), "v"(acc[1][NT - 1]), "v"(acc[2][NT - 1]), "v"(acc[3][NT - 1]));   // all MFMAs done
-#endif
-        BSTAMP(bt1)
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             float4 hq[4];
@@ -1958,45 +1823,13 @@ __global__ __launch_bounds__(512, 2) void time_lstm_bf16_kernel(TimeLstmArgs a) 
                 }
             }
         }
-        BSTAMP(bt2)
         __syncthreads();   // h_s complete in the other buffer before anyone reads it; this one free for step s+1's writes
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-        BSTAMP(bt3)
-        if (s > 0) { bv_k += bt1 - bt0; bv_cell += bt2 - bt1; bv_bar += bt3 - bt2; }
-#endif
     }
-#if defined(SDFA_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-    if (NT == 2 && lane == 0) { atomicAdd(&g_lsub[0], bv_k); atomicAdd(&g_lsub[1], bv_cell); atomicAdd(&g_lsub[2], bv_bar); atomicAdd(&g_lsub[3], 63ull); }
-#endif
-#undef BSTAMP
 #undef TB_GX
 #undef TB_W
 }
 
 }  // namespace
-
-#ifdef SDFA_STAMPS
-extern "C" int sdfa_debug_read_lstm_stamps(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lstamp), sizeof(unsigned long long) * 8) != hipSuccess) return -3;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_lstamp), z, sizeof z) != hipSuccess) return -3; }
-    return 0;
-}
-extern "C" int sdfa_debug_read_lstm_sub(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lsub), sizeof(unsigned long long) * 4) != hipSuccess) return -3;
-    if (reset) { unsigned long long z[4] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_lsub), z, sizeof z) != hipSuccess) return -3; }
-    return 0;
-}
-extern "C" int sdfa_debug_read_lstm_xcd(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lxcd), sizeof(unsigned long long) * 32) != hipSuccess) return -3;
-    if (reset) { unsigned long long z[32] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_lxcd), z, sizeof z) != hipSuccess) return -3; }
-    return 0;
-}
-extern "C" int sdfa_debug_read_lstm_span(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lspan), sizeof(unsigned long long) * 4) != hipSuccess) return -3;
-    if (reset) { unsigned long long z[4] = {~0ull, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_lspan), z, sizeof z) != hipSuccess) return -3; }
-    return 0;
-}
-#endif
 
 // Launch forms of the fp32 recurrence (FreqLstmArgs::shape; all bit-identical):
 //   9  freq_lstm_v3_kernel, persistent (tile queue), one workgroup per CU   -- default
@@ -2033,11 +1866,7 @@ static hipError_t launch_freq(const FreqLstmArgs &a, hipStream_t s) {
         hipLaunchKernelGGL((freq_lstm_v2_kernel<SHARED, true>), dim3(n_tiles < slots ? n_tiles : slots), dim3(256), 0, s, a);
         return hipGetLastError();
     }
-    size_t lone = 0;
-#ifdef SDFA_STAMPS
-    if (getenv("SDFA_LONE")) lone = 32 * 1024;      // diagnostic: 32 KB of unused dynamic LDS = one workgroup per CU
-#endif
-    hipLaunchKernelGGL((freq_lstm_v2_kernel<SHARED, false>), dim3(n_tiles), dim3(256), lone, s, a);
+    hipLaunchKernelGGL((freq_lstm_v2_kernel<SHARED, false>), dim3(n_tiles), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

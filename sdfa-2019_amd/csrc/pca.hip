@@ -374,9 +374,6 @@ __global__ __launch_bounds__(256, 1) void pca_dgrad_res_kernel(PcaArgs a, int *q
 #undef PR_BR
             }
             }
-#ifdef SDFA_PR_NOEPI   /* timing experiment only: how long do the K loops alone take? */
-            if (accs[0][0][0] + accr[0][0][0] != 123.456f) continue;
-#endif
             if (frame0 >= a.N) continue;                   // a wave of padding frames (its MFMAs ran on zeros; nothing to store)
             // epilogue: 16 passes of two frames (accumulator rows 8g + 4h + e): transpose through LDS, whole-row 16-byte stores,
             // software-pipelined -- pass p's LDS writes (row pair p & 1) are issued while pass p-1's read-back (other pair) is in
@@ -408,20 +405,6 @@ __global__ __launch_bounds__(256, 1) void pca_dgrad_res_kernel(PcaArgs a, int *q
             }
             float4 rv0, rv1, rv2;      // (named: an array indexed inside the destination loop ends up in scratch memory)
             const bool plain = frame0 + 32 <= a.N && orow_valid >= 288 && a.n_extra == 0;      // uniform
-#ifdef SDFA_PCA_DIRECT   /* experiment: no LDS transposition -- every lane stores its own 4-byte values (144 dword stores
-                            per lane and tile instead of 48 x 16 bytes); correct results for whole tiles with one destination */
-            if (plain) {
-#pragma unroll
-                for (int p = 0; p < 16; ++p) {
-                    float *orow = a.out + (frame0 + 8 * (p >> 2) + (p & 3) + 4 * h) * a.out_dim + ocol0;
-#pragma unroll
-                    for (int t = 0; t < 6; ++t) orow[opos[t]] = accs[0][t][p] + mean[t];
-#pragma unroll
-                    for (int t = 0; t < 3; ++t) orow[opos[6 + t]] = accr[0][t][p] + mean[6 + t];
-                }
-                continue;
-            }
-#endif
             PR_WRITE(0)
             WAVE_LDS_FENCE()
             PR_READ(0)
