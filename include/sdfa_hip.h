@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define SDFA_ABI_VERSION 5   /* bumped whenever an export is added or a signature changes: the Python binding refuses a library of another version with
-                                "stale library, run make" instead of a bare AttributeError.  5: + sdfa_debug_frontend_status (added in round 5 without a bump);
+                                "stale library, run make" instead of a bare AttributeError.  5: + sdfa_debug_frontend_status (added in round 5 without a bump),
+                                + sdfa_mesh_deform_grad (additive; a library without it fails the binding's symbol check at import);
                                 4: workspace status block (sdfa_workspace_init / _status*, replaces sdfa_debug_time_lstm_timeout), unaligned sdfa_ensemble_mean (round 4);
                                 3: + sdfa_ensemble_mean, sdfa_model_set_reserved_cus, sdfa_debug_time_lstm_timeout (round 3); 2: + seek, resample, mesh correspondences,
                                 multi-destination regress, expand_coef, autotune (round 2); all earlier entry points unchanged */
@@ -374,6 +375,26 @@ sdfa_mesh *sdfa_mesh_create_corres(const float *h_verts, int64_t n_verts, const 
                                    const uint32_t *h_cnsts, int64_t n_cnsts, const uint32_t *h_corr_count,
                                    const uint32_t *h_corr_faces, int64_t n_corr_faces, int64_t n_src_tris, double reg,
                                    void *stream);
+
+/* mesh -> dgrad, the opposite direction: deformation.get_deform_grad(verts_a, verts_b, faces, eps)
+ * (deformation/cpp/src/pybind.cpp:78-99; deform_triangle_impl.hpp:143-213,447-470; rotation/utils_rotation.cpp log), batched over
+ * frames, fp64 inside.  Per triangle: frames [e1 e2 e3] of source and target, T = B A^-1, polar decomposition through a Jacobi SVD
+ * (singular values descending, the smallest flipped when det < 0), R = U diag(1,1,d) V^T, scale = V diag(1,1,d) S V^T ->
+ *   [s00-1, s01, s02, s11-1, s12, s22-1, logR01, logR02, logR12]
+ * A triangle degenerate on either mesh (|cos(e1, e2)| > 1 - eps) or set in d_tri_mask gets 9 exact zeros.
+ *   d_src_verts  [n_verts][3] float32 source (template) vertices
+ *   d_target     [n_frames][n_verts][3] float32: target vertices, or (target_is_offsets != 0) per-vertex offsets, the target then
+ *                being float32(source + offset) as the reference's preload.py forms it
+ *   d_faces      [n_tris][3] uint32 (an index >= n_verts is never read: its row is NaN)
+ *   d_tri_mask   [n_tris] uint8, nonzero = zeroed (the non-face triangles of preload.py:778); NULL = none
+ *   out_dtype    SDFA_DTYPE_F32: d_out float [n_frames][n_tris*9] (the rows sdfa_mesh_from_dgrad* consume), the float64 result
+ *                rounded once;  SDFA_DTYPE_F64: d_out double [n_frames][n_tris*9]
+ * Never synchronises. */
+#define SDFA_DTYPE_F32 0
+#define SDFA_DTYPE_F64 1
+int     sdfa_mesh_deform_grad(const float *d_src_verts, const float *d_target, int target_is_offsets, int64_t n_frames,
+                              int64_t n_verts, const uint32_t *d_faces, int64_t n_tris, const uint8_t *d_tri_mask, double eps,
+                              int out_dtype, void *d_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * NEXT ROW: frame-time resampling, saber.stream.seek

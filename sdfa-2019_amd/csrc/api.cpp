@@ -1685,6 +1685,22 @@ int sdfa_mesh_from_dgrad_seek(const sdfa_mesh *m, const float *d_dgrad, const in
 int64_t sdfa_mesh_n_verts(const sdfa_mesh *m) { return m ? m->n_verts : fail(SDFA_EINVAL, "null mesh"); }
 int64_t sdfa_mesh_n_src_tris(const sdfa_mesh *m) { return m ? m->n_src_tris : fail(SDFA_EINVAL, "null mesh"); }
 
+int sdfa_mesh_deform_grad(const float *d_src_verts, const float *d_target, int target_is_offsets, int64_t n_frames, int64_t n_verts,
+                          const uint32_t *d_faces, int64_t n_tris, const uint8_t *d_tri_mask, double eps, int out_dtype, void *d_out,
+                          void *stream) {
+    if (n_frames < 0 || n_verts <= 0 || n_tris <= 0 || n_verts > INT32_MAX || n_tris > INT32_MAX / 9)
+        return fail(SDFA_EINVAL, "mesh_deform_grad: bad counts");
+    if (out_dtype != SDFA_DTYPE_F32 && out_dtype != SDFA_DTYPE_F64) return fail(SDFA_EINVAL, "mesh_deform_grad: out_dtype must be SDFA_DTYPE_F32 or SDFA_DTYPE_F64");
+    if (n_frames == 0) return SDFA_OK;
+    if (!d_src_verts || !d_target || !d_faces || !d_out) return fail(SDFA_EINVAL, "mesh_deform_grad: null pointer");
+    DgradArgs a{};
+    a.src = d_src_verts; a.target = d_target; a.faces = d_faces; a.mask = d_tri_mask;
+    a.n_frames = n_frames; a.n_tris = (int)n_tris; a.n_verts = (int)n_verts; a.target_is_offsets = target_is_offsets != 0; a.eps = eps;
+    if (out_dtype == SDFA_DTYPE_F64) a.out64 = (double *)d_out; else a.out32 = (float *)d_out;
+    HIP_TRY(sdfa_launch_deform_grad(a, (hipStream_t)stream));
+    return SDFA_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // saber.stream.seek (saber/data/stream/stream.py:20-46) for the uniform video-rate queries of model.py:204-212
 int64_t sdfa_seek_query_count(int32_t last_timestamp_ms, double fps) {

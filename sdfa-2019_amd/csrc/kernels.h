@@ -240,6 +240,19 @@ hipError_t sdfa_launch_mesh_scatter(const MeshArgs &a, hipStream_t s);
 hipError_t sdfa_launch_seek_plan(const int32_t *tslist, const int64_t *frame_off, const int64_t *query_off, int n_clips, double fps,
                                  int64_t n_queries, int64_t *src, float *w, hipStream_t s);
 hipError_t sdfa_launch_seek_rows(const float *rows, int64_t width, const int64_t *src, const float *w, int64_t nq, float *out, hipStream_t s);
+// mesh -> dgrad (dgrad.hip): deformation gradients of per-frame target meshes against one source mesh, one thread per (frame, triangle)
+struct DgradArgs {
+    const float *src;          // [n_verts][3] source vertices
+    const float *target;       // [n_frames][n_verts][3] target vertices, or offsets added to src (target_is_offsets)
+    const uint32_t *faces;     // [n_tris][3]
+    const uint8_t *mask;       // [n_tris] nonzero = 9 exact zeros (null: none)
+    int64_t n_frames;
+    int n_tris, n_verts, target_is_offsets;
+    double eps;
+    float *out32;              // [n_frames][n_tris * 9] when out64 is null
+    double *out64;             // [n_frames][n_tris * 9]
+};
+hipError_t sdfa_launch_deform_grad(const DgradArgs &a, hipStream_t s);
 // test-time ensembling: out = (a + b) / 2, element-wise, float32 roundings of numpy's `sum += x; sum / 2.0` (vector path for 16-byte aligned pointers)
 hipError_t sdfa_launch_ensemble_mean(const float *a, const float *b, int64_t n, float *out, hipStream_t s);
 

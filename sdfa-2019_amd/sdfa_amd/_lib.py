@@ -60,6 +60,7 @@ SYMBOLS = {
     "sdfa_mesh_n_verts": (_i64, [_p]),
     "sdfa_mesh_n_src_tris": (_i64, [_p]),
     "sdfa_mesh_create_corres": (_p, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i64, C.c_double, _p]),
+    "sdfa_mesh_deform_grad": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p, _i64, _p, C.c_double, C.c_int, _p, _p]),
     "sdfa_seek_query_count": (_i64, [_i32, C.c_double]),
     "sdfa_seek_plan": (C.c_int, [_p, _p, _p, _i32, C.c_double, _i64, _p, _p, _p]),
     "sdfa_seek_rows": (C.c_int, [_p, _i64, _p, _p, _i64, _p, _p]),

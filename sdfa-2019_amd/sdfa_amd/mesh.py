@@ -94,3 +94,69 @@ class MeshSolver:
                                                 C.c_void_p(plan.w.data_ptr()), n, C.c_void_p(out.data_ptr()),
                                                 C.c_void_p(ws.data_ptr()), ws.numel(), _stream()))
         return out
+
+
+def _check_faces(faces, n_verts):
+    f = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3))
+    if len(f) == 0:
+        raise ValueError("deform_grad: no faces")
+    if f.min() < 0 or f.max() >= n_verts:
+        raise ValueError(f"deform_grad: face index out of range [0, {n_verts})")
+    return f.astype(np.uint32)
+
+
+class DeformGrad:
+    """mesh -> dgrad on the device (sdfa_mesh_deform_grad): the source mesh, the faces and an optional per-triangle mask are uploaded
+    once; every call turns a batch of target frames -- vertices, or offsets from the source -- into dgrad rows [F, n_tris*9] on the
+    device.  `tri_mask` (n_tris booleans) zeroes those triangles, as the reference's preload.py zeroes the non-face ones."""
+
+    def __init__(self, src_verts, faces, tri_mask=None, eps=1e-6, device="cuda:0"):
+        v = np.ascontiguousarray(np.asarray(src_verts, np.float32).reshape(-1, 3))
+        f = _check_faces(faces, len(v))
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeformGrad needs a ROCm GPU: there is no CPU implementation")
+        self.device = torch.device(device)
+        self.n_verts, self.n_tris, self.eps = len(v), len(f), float(eps)
+        self.src = torch.from_numpy(v).to(self.device)
+        self.faces = torch.from_numpy(f.view(np.int32)).to(self.device)
+        self.mask = None
+        if tri_mask is not None:
+            m = np.asarray(tri_mask).reshape(-1)
+            if len(m) != self.n_tris:
+                raise ValueError(f"deform_grad: tri_mask needs one entry per triangle ({self.n_tris}), got {len(m)}")
+            self.mask = torch.from_numpy(m.astype(bool).astype(np.uint8)).to(self.device)
+
+    def __call__(self, target, offsets=False, dtype=torch.float32, out=None):
+        """target: (F, n_verts*3) / (F, n_verts, 3) float32 cuda rows of vertices, or of offsets added to the source in float32
+        (`offsets=True`) -> (F, n_tris*9) `dtype` (float32: the float64 result rounded once, or float64) on the device."""
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("deform_grad: dtype must be torch.float32 or torch.float64")
+        t = target.to(device=self.device, dtype=torch.float32)
+        t = t.reshape(t.shape[0], -1).contiguous()
+        if t.shape[1] != self.n_verts * 3:
+            raise ValueError(f"deform_grad: target rows must hold {self.n_verts * 3} values, got {t.shape[1]}")
+        n = t.shape[0]
+        if out is None:
+            out = torch.empty((n, self.n_tris * 9), dtype=dtype, device=self.device)
+        assert out.dtype == dtype and out.is_contiguous() and out.numel() == n * self.n_tris * 9
+        with torch.cuda.device(self.device):
+            check(lib.sdfa_mesh_deform_grad(C.c_void_p(self.src.data_ptr()), C.c_void_p(t.data_ptr()), int(bool(offsets)), n,
+                                            self.n_verts, C.c_void_p(self.faces.data_ptr()), self.n_tris,
+                                            C.c_void_p(self.mask.data_ptr()) if self.mask is not None else None, self.eps,
+                                            1 if dtype == torch.float64 else 0, C.c_void_p(out.data_ptr()), _stream()))
+        return out
+
+
+def deform_grad(verts_a, verts_b, faces, eps=1e-6, device="cuda:0"):
+    """deformation.get_deform_grad(verts_a, verts_b, faces, eps) (deformation/cpp/src/pybind.cpp:78-99), computed on the GPU.
+    The vertices are taken as float32, as the reference's binding casts them.  verts_b one frame (V, 3) -> float64 (n_tris*9,);
+    verts_b (F, V, 3) -> float64 (F, n_tris*9)."""
+    a = np.ascontiguousarray(np.asarray(verts_a, np.float32).reshape(-1, 3))
+    b = np.asarray(verts_b, np.float32)
+    single = b.ndim <= 2
+    b = np.ascontiguousarray(b.reshape(-1, a.size))
+    if b.shape[1] != a.size:
+        raise ValueError("deform_grad: verts_a and verts_b differ in size")
+    dg = DeformGrad(a, faces, eps=eps, device=device)
+    out = dg(torch.from_numpy(b), dtype=torch.float64).cpu().numpy()
+    return out[0] if single else out

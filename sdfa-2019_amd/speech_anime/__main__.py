@@ -25,6 +25,9 @@ def _parser():
             ap.add_argument("--" + name, type=typ, default=default)
     # not a reference flag: who encodes the --save_video frames to JPEG (host PIL threads or the GPU; the same bytes)
     ap.add_argument("--jpeg_encoder", choices=["pil", "gpu"], default="pil")
+    # not a reference flag: the FLAME neutral .obj the offsets head's rows are measured from; with it the offsets head is retargeted to
+    # --template_mesh (any topology, through --mesh_tricorres) by the deformation transfer the dgrad head uses
+    ap.add_argument("--source_mesh", type=str, default=None)
     return ap
 
 

@@ -44,6 +44,11 @@ def evaluate_model(args):
     if args.get("save_video") and not args.get("template_mesh"):       # before any file or device work
         raise ValueError("--save_video needs --template_mesh <obj>: the video is rendered from the template mesh (the reference falls "
                          "back to its bundled FLAME_sample.obj, which is not part of this tree)")
+    if args.get("source_mesh"):                                         # not a reference flag: retarget the offsets head
+        if not args.get("template_mesh"):
+            raise ValueError("--source_mesh needs --template_mesh <obj>: the offsets are retargeted onto that template")
+        from . import viewer
+        viewer.set_source_mesh(args["source_mesh"])                     # refuses a non-FLAME source before any device work
     hparams = configure(args)
     if hparams.eval_input is not None:                                  # api.py:83-87
         rec = [hparams.eval_input]

@@ -293,6 +293,9 @@ class SaberSpeechDrivenAnimation:
         from .. import video as _video
         if jpeg_encoder not in _video.JPEG_ENCODERS:
             raise ValueError(f"jpeg_encoder must be one of {_video.JPEG_ENCODERS}, not {jpeg_encoder!r}")
+        if kwargs.get("source_mesh") is not None:       # not a reference kwarg: retarget the offsets head (viewer.set_source_mesh)
+            from .. import viewer
+            viewer.set_source_mesh(kwargs["source_mesh"])
         if save_video:
             from .. import viewer
             if not viewer.has_template():
@@ -393,6 +396,8 @@ class SaberSpeechDrivenAnimation:
             if viewer.has_template():          # --template_mesh given: seek + solve on the GPU, then .obj per frame
                 if self._face_type == "dgrad_3d":
                     verts, faces = viewer.track_to_mesh(track, plan).cpu().numpy(), viewer.template_faces()
+                elif viewer.has_source_mesh():     # offsets head retargeted on the device: deform_grad + the template's solve
+                    verts, faces = viewer._device_verts(plan.rows(track), self._face_type).cpu().numpy(), viewer.template_faces()
                 else:
                     verts, faces = viewer.frames_to_mesh(frames.astype(np.float32), self._face_type)
                 for i_frame in range(len(frames)):

@@ -38,6 +38,13 @@ def write_obj(path, verts, faces):
 
 
 N_MODEL_TRIS = 9976      # triangles of the model's FLAME-topology dgrad rows (frame.py:117: 89784 = 9976 * 9)
+N_MODEL_VERTS = 5023     # vertices of the model's FLAME-topology offsets rows (15069 = 5023 * 3)
+
+# --source_mesh (not a reference flag): the FLAME neutral the offsets head's rows are measured from.  Set, the offsets head is
+# retargeted like the dgrad head -- offsets -> deform_grad(source, source + offsets), non-face triangles zeroed (preload.py:768-779)
+# -> the template's solve -- so --template_mesh may be of another topology.  Host copies; the device form is made on first use.
+_source = None           # dict(verts, faces, mask) of the validated source mesh
+_source_dev = {}         # device -> sdfa_amd.mesh.DeformGrad of it
 
 
 def set_dgrad_static(verts, faces, c_indices=None, corres=None):
@@ -108,6 +115,44 @@ def template_faces():
     return _template_faces
 
 
+def set_source_mesh(source):
+    """The FLAME-topology source of the offsets head: an .obj path or (verts, faces).  Validated here, before any device work:
+    anything but 5,023 vertices and 9,976 triangles is refused."""
+    global _source
+    verts, faces = read_obj(source) if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__") else source
+    verts = np.asarray(verts, np.float32).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3)
+    if (len(verts), len(faces)) != (N_MODEL_VERTS, N_MODEL_TRIS):
+        raise ValueError(f"source mesh must have the FLAME topology of the offsets head ({N_MODEL_VERTS} vertices, {N_MODEL_TRIS} "
+                         f"triangles), got {len(verts)} vertices and {len(faces)} triangles")
+    if faces.min() < 0 or faces.max() >= N_MODEL_VERTS:
+        raise ValueError("source mesh: face index out of range")
+    from .datasets.vocaset_mask import non_face_tris
+    _source = dict(verts=verts, faces=faces.astype(np.uint32), mask=non_face_tris(faces))
+    _source_dev.clear()
+
+
+def clear_source_mesh():
+    global _source
+    _source = None
+    _source_dev.clear()
+
+
+def has_source_mesh():
+    return _source is not None
+
+
+def source_dgrad(offsets_rows):
+    """(n, 15069) float32 cuda offsets rows -> (n, 89784) float32 dgrad rows on the device, as preload.py:768-779 makes them:
+    deform_grad(source, float32(source + offsets)), the non-face triangles zeroed."""
+    assert _source is not None, "set_source_mesh first"
+    dev = offsets_rows.device
+    if dev not in _source_dev:
+        from sdfa_amd.mesh import DeformGrad
+        _source_dev[dev] = DeformGrad(_source["verts"], _source["faces"], tri_mask=_source["mask"], device=dev)
+    return _source_dev[dev](offsets_rows, offsets=True)
+
+
 def frames_to_mesh(data_frames, face_data_type):
     """Batched frame_to_mesh: (n, 9976, 9) / (n, 89784) dgrad or (n, 15069) offsets -> (verts (n, V, 3) numpy, faces)."""
     assert _solver is not None, "set_template_mesh first"
@@ -115,6 +160,8 @@ def frames_to_mesh(data_frames, face_data_type):
     n = x.shape[0]
     if str(face_data_type).endswith("dgrad_3d"):
         verts = _solver.get_mesh(x.reshape(n, -1)).cpu().numpy()
+    elif str(face_data_type).endswith("verts_off_3d") and _source is not None:
+        verts = _device_verts(x.to(device=_solver.device, dtype=torch.float32), face_data_type).cpu().numpy()
     elif str(face_data_type).endswith("verts_off_3d"):
         verts = x.reshape(n, -1, 3).cpu().numpy() + _template_verts[None]
     else:
@@ -152,6 +199,8 @@ def _device_verts(x, face_data_type):
     n = x.shape[0]
     if str(face_data_type).endswith("dgrad_3d"):
         return _solver.get_mesh(x.reshape(n, -1))
+    if str(face_data_type).endswith("verts_off_3d") and _source is not None:      # retargeted: offsets -> dgrad -> template solve
+        return _solver.get_mesh(source_dgrad(x.reshape(n, -1)))
     if str(face_data_type).endswith("verts_off_3d"):
         return x.reshape(n, -1, 3) + torch.from_numpy(_template_verts).to(x.device)[None]
     return x.reshape(n, -1, 3)
@@ -168,7 +217,7 @@ def render_frame(frame, face_data_type, image_size=(512, 512)):
 def render_track(anime_rows, plan, image_size=(512, 512), face_data_type="dgrad_3d", n=None, samples=4):
     """model.py:204-223 for one batch of clips as device stages: the animation-rate rows (n_frames, ...) on the GPU and a
     sdfa_amd.seek.SeekPlan -> images of the first `n` (default: all) video frames, (n, H, W, 3) uint8 cuda.  dgrad: seek + solve +
-    render; offsets: seek, + template, render -- the vertices never leave the device."""
+    render; offsets: seek, + template (or, with a source mesh, deform_grad + solve), render -- the vertices never leave the device."""
     assert _solver is not None, "set_template_mesh first"
     if str(face_data_type).endswith("dgrad_3d"):
         verts = _solver.get_mesh_seek(anime_rows, plan)
