@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256, 2) void conv123_kernel(ConvArgs a) {
 // 37 + 24 + 4 per wave instead of 281 fp32 MFMAs of twice the cycles.  The K axes are ordered so that every lane builds its B
 // operand from values it already owns (the scheme of the LSTM kernels): an accumulator lane holds channels 8g + 4h + e (g, e = 0..3),
 // so k-step "octet pair q" of lane half h is channels {8(2q) + 4h + e} u {8(2q+1) + 4h + e} -- pool1 goes to LDS as such octets,
-// plane by plane, and pool2 never leaves the registers.  The host packs the weights in the same order (api.cpp: pack_conv_bf16).
+// plane by plane, and pool2 never leaves the registers.  The host packs the weights in the same order (api_model.cpp: pack_conv_bf16).
 typedef __bf16 cbf16x8 __attribute__((ext_vector_type(8)));
 #define CMFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 

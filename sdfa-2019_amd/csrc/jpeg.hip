@@ -23,10 +23,10 @@
 // and max_frame_bytes bounds every file (see the header), so no kernel can write past its buffers.
 #include "../../include/sdfa_jpeg.h"
 #include "../../include/sdfa_hip.h"
+#include "host.h"
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -419,22 +419,6 @@ struct sdfa_jpeg_encoder {
 
 namespace {
 
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    sdfa_failv(code, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define JPEG_HIP_TRY(expr)                                                                               \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess) return fail(SDFA_EHIP, "%s failed: %s", #expr, hipGetErrorString(e__));   \
-    } while (0)
-
-int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
 struct Layout {
     int64_t coefs, blen, boff, fbits, words, total;
 };
@@ -471,16 +455,16 @@ std::vector<uint8_t> with(std::vector<uint8_t> v, const uint8_t *a, int n) {
 }
 
 int check_rgb(const sdfa_jpeg_encoder *e, const uint8_t *d_rgb, int64_t n, const char *who) {
-    if (!e) return fail(SDFA_EINVAL, "%s: null encoder", who);
-    if (n < 0 || n > SDFA_JPEG_MAX_FRAMES) return fail(SDFA_EINVAL, "%s: frame count %lld outside 0 .. %d", who, (long long)n, SDFA_JPEG_MAX_FRAMES);
-    if (n > 0 && !d_rgb) return fail(SDFA_EINVAL, "%s: null input", who);
+    if (!e) return sdfa_fail(SDFA_EINVAL, "%s: null encoder", who);
+    if (n < 0 || n > SDFA_JPEG_MAX_FRAMES) return sdfa_fail(SDFA_EINVAL, "%s: frame count %lld outside 0 .. %d", who, (long long)n, SDFA_JPEG_MAX_FRAMES);
+    if (n > 0 && !d_rgb) return sdfa_fail(SDFA_EINVAL, "%s: null input", who);
     return SDFA_OK;
 }
 
 int launch_transform(const sdfa_jpeg_encoder *e, const uint8_t *d_rgb, int64_t n, int16_t *coefs, hipStream_t s) {
     const dim3 grid((unsigned)((e->g.nmcu + MCUS_PER_WG - 1) / MCUS_PER_WG), (unsigned)n);
     hipLaunchKernelGGL(jpeg_transform_kernel, grid, dim3(TF_THREADS), 0, s, d_rgb, e->g, e->q, coefs);
-    JPEG_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SDFA_OK;
 }
 
@@ -492,10 +476,10 @@ int sdfa_jpeg_abi_version(void) { return SDFA_JPEG_ABI_VERSION; }
 
 sdfa_jpeg_encoder *sdfa_jpeg_create(int width, int height, int quality, void *stream) {
     if (width < 1 || height < 1 || width > SDFA_JPEG_MAX_SIDE || height > SDFA_JPEG_MAX_SIDE) {
-        fail(SDFA_EINVAL, "jpeg_create: image size %d x %d outside 1 .. %d", width, height, SDFA_JPEG_MAX_SIDE);
+        sdfa_fail(SDFA_EINVAL, "jpeg_create: image size %d x %d outside 1 .. %d", width, height, SDFA_JPEG_MAX_SIDE);
         return nullptr;
     }
-    if (quality < 1 || quality > 100) { fail(SDFA_EINVAL, "jpeg_create: quality %d outside 1 .. 100", quality); return nullptr; }
+    if (quality < 1 || quality > 100) { sdfa_fail(SDFA_EINVAL, "jpeg_create: quality %d outside 1 .. 100", quality); return nullptr; }
     sdfa_jpeg_encoder *e = new sdfa_jpeg_encoder();
     Geometry &g = e->g;
     g.W = width; g.H = height;
@@ -544,7 +528,7 @@ sdfa_jpeg_encoder *sdfa_jpeg_create(int width, int height, int quality, void *st
 
     hipStream_t s = (hipStream_t)stream;
     auto bail = [&](const char *what, hipError_t err) -> sdfa_jpeg_encoder * {
-        fail(SDFA_EHIP, "jpeg_create: %s failed: %s", what, hipGetErrorString(err));
+        sdfa_fail(SDFA_EHIP, "jpeg_create: %s failed: %s", what, hipGetErrorString(err));
         sdfa_jpeg_destroy(e);
         return nullptr;
     };
@@ -565,19 +549,19 @@ void sdfa_jpeg_destroy(sdfa_jpeg_encoder *e) {
 }
 
 int64_t sdfa_jpeg_header(const sdfa_jpeg_encoder *e, uint8_t *h_out, int64_t capacity) {
-    if (!e || capacity < 0) return fail(SDFA_EINVAL, "jpeg_header: bad argument");
+    if (!e || capacity < 0) return sdfa_fail(SDFA_EINVAL, "jpeg_header: bad argument");
     const int64_t len = (int64_t)e->header.size();
     if (h_out) memcpy(h_out, e->header.data(), (size_t)(capacity < len ? capacity : len));
     return len;
 }
 
 int64_t sdfa_jpeg_max_frame_bytes(const sdfa_jpeg_encoder *e) {
-    if (!e) return fail(SDFA_EINVAL, "jpeg_max_frame_bytes: null encoder");
+    if (!e) return sdfa_fail(SDFA_EINVAL, "jpeg_max_frame_bytes: null encoder");
     return e->max_frame_bytes;
 }
 
 int64_t sdfa_jpeg_workspace_bytes(const sdfa_jpeg_encoder *e, int64_t n) {
-    if (!e || n < 0) return fail(SDFA_EINVAL, "jpeg_workspace_bytes: bad argument");
+    if (!e || n < 0) return sdfa_fail(SDFA_EINVAL, "jpeg_workspace_bytes: bad argument");
     return layout(e, n).total;
 }
 
@@ -585,14 +569,14 @@ int sdfa_jpeg_encode(sdfa_jpeg_encoder *e, const uint8_t *d_rgb, int64_t n, uint
                      int64_t *d_offsets, int64_t *d_lengths, void *d_ws, int64_t ws_bytes, void *stream) {
     int rc = check_rgb(e, d_rgb, n, "jpeg_encode");
     if (rc < 0 || n == 0) return rc;
-    if (!d_out || !d_offsets || !d_lengths || !d_ws) return fail(SDFA_EINVAL, "jpeg_encode: null pointer");
+    if (!d_out || !d_offsets || !d_lengths || !d_ws) return sdfa_fail(SDFA_EINVAL, "jpeg_encode: null pointer");
     if (out_capacity < n * e->max_frame_bytes)
-        return fail(SDFA_ENOSPACE, "jpeg_encode: output of %lld bytes, %lld frames need %lld", (long long)out_capacity, (long long)n,
+        return sdfa_fail(SDFA_ENOSPACE, "jpeg_encode: output of %lld bytes, %lld frames need %lld", (long long)out_capacity, (long long)n,
                     (long long)(n * e->max_frame_bytes));
-    if ((uintptr_t)d_ws & 255) return fail(SDFA_EINVAL, "jpeg_encode: workspace must be 256-byte aligned");
+    if ((uintptr_t)d_ws & 255) return sdfa_fail(SDFA_EINVAL, "jpeg_encode: workspace must be 256-byte aligned");
     const Layout l = layout(e, n);
     if (ws_bytes < l.total)
-        return fail(SDFA_ENOSPACE, "jpeg_encode: workspace of %lld bytes, %lld needed for %lld frames", (long long)ws_bytes,
+        return sdfa_fail(SDFA_ENOSPACE, "jpeg_encode: workspace of %lld bytes, %lld needed for %lld frames", (long long)ws_bytes,
                     (long long)l.total, (long long)n);
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)d_ws;
@@ -602,29 +586,29 @@ int sdfa_jpeg_encode(sdfa_jpeg_encoder *e, const uint8_t *d_rgb, int64_t n, uint
     unsigned long long *words = (unsigned long long *)(ws + l.words);
     const int64_t hdr_len = (int64_t)e->header.size();
 
-    JPEG_HIP_TRY(hipMemsetAsync(words, 0, (size_t)(n * e->cap_words * 8), s));
+    HIP_TRY(hipMemsetAsync(words, 0, (size_t)(n * e->cap_words * 8), s));
     if ((rc = launch_transform(e, d_rgb, n, coefs, s)) < 0) return rc;
     const dim3 gb((unsigned)((e->nblk + 3) / 4), (unsigned)n);
     hipLaunchKernelGGL(jpeg_bits_kernel<false>, gb, dim3(256), 0, s, coefs, e->nblk, e->d_huff, blen, nullptr, nullptr, e->cap_words);
-    JPEG_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(jpeg_scan_kernel<int>, dim3((unsigned)n), dim3(SCAN_THREADS), 0, s, blen, e->nblk, boff, fbits);
-    JPEG_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(jpeg_bits_kernel<true>, gb, dim3(256), 0, s, coefs, e->nblk, e->d_huff, nullptr, boff, words, e->cap_words);
-    JPEG_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, s, words, e->cap_words, fbits, hdr_len, d_lengths);
-    JPEG_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(jpeg_scan_kernel<int64_t>, dim3(1), dim3(SCAN_THREADS), 0, s, d_lengths, n, d_offsets, nullptr);
-    JPEG_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(jpeg_emit_kernel, dim3((unsigned)n), dim3(SCAN_THREADS), 0, s, words, e->cap_words, fbits, e->d_header,
                        hdr_len, d_offsets, d_lengths, d_out);
-    JPEG_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SDFA_OK;
 }
 
 int sdfa_jpeg_debug_coefs(sdfa_jpeg_encoder *e, const uint8_t *d_rgb, int64_t n, int16_t *d_coefs, void *stream) {
     int rc = check_rgb(e, d_rgb, n, "jpeg_debug_coefs");
     if (rc < 0 || n == 0) return rc;
-    if (!d_coefs) return fail(SDFA_EINVAL, "jpeg_debug_coefs: null output");
+    if (!d_coefs) return sdfa_fail(SDFA_EINVAL, "jpeg_debug_coefs: null output");
     return launch_transform(e, d_rgb, n, d_coefs, (hipStream_t)stream);
 }
 

@@ -1,12 +1,7 @@
-// Internal launcher interface between api.cpp (host orchestration) and the .hip kernel files.
+// Internal launcher interface between the api_*.cpp files (host orchestration) and the .hip kernel files.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-
-// Records the message sdfa_last_error() returns (api.cpp) and returns `code`: the error path of the files with C entry
-// points of their own (render.hip).
-int sdfa_failv(int code, const char *fmt, va_list ap);
 
 enum { ACT_NONE = 0, ACT_LRELU = 1, ACT_TANH = 2 };
 
@@ -57,7 +52,7 @@ struct PcaArgs {
     int n_extra;
     int reserve_cus;                 // pca_dgrad_res_kernel: launch (CUs - reserve_cus) workgroups
     // split-bf16 form of pca_dgrad_res_kernel (terms == 3): both bases as bf16 octets, per triangle block
-    // [plane hi | lo][scale rows 2 ks + h (12) x 192 columns | rotat rows (24) x 96] (api.cpp: pack_pca_bf16); null / other terms = fp32
+    // [plane hi | lo][scale rows 2 ks + h (12) x 192 columns | rotat rows (24) x 96] (api_model.cpp: pack_pca_bf16); null / other terms = fp32
     const void *basis_b;
     int terms;
 };
@@ -107,7 +102,7 @@ struct ConvArgs {
     const int32_t *col_src;
     const int64_t *col_limit;
     // mixed-precision modes (sdfa_launch_conv123 only): bf16 planes [hi | mid | lo] of the three layers' weights in the K order of
-    // conv123_bf16_kernel (api.cpp: pack_conv_bf16); terms 0 = fp32 MFMA, 1 / 3 / 6 as in FreqLstmArgs
+    // conv123_bf16_kernel (api_model.cpp: pack_conv_bf16); terms 0 = fp32 MFMA, 1 / 3 / 6 as in FreqLstmArgs
     const void *wb;
     int terms;
 };
@@ -142,7 +137,7 @@ struct TimeLstmArgs {
     int terms;           // 0 = fp32 MFMA; 1 = bf16; 3 = split-bf16
     unsigned *flags;     // small-batch form (time_lstm_split_kernel): [0] this launch's time-out word, [4 ..] one flag per workgroup; null = never split
     int64_t flag_words;  // words available at `flags`
-    const float *W16;    // time_lstm_split16_kernel: per direction float4 [16 K16][4 g][1024 rows] (api.cpp pack_rec_16x16x4); null = not packed
+    const float *W16;    // time_lstm_split16_kernel: per direction float4 [16 K16][4 g][1024 rows] (api_model.cpp pack_rec_16x16x4); null = not packed
     unsigned *status;    // word 0 of the workspace's status block: counts the waits of the small-batch form that expired (null = not counted)
     int reserve_cus;     // the small-batch form is used while its grid fits (CUs - reserve_cus)
     const int32_t *col_map;   // column sharing, layer 0: GX holds the DISTINCT columns; column (t, n) reads GX column col_map[t * Nc + n] (null = its own)

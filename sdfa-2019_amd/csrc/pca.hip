@@ -133,7 +133,7 @@ constexpr int PR_RS = 2 * PR_KS, PR_RR = 2 * PR_KR;   // their k-quad rows
 
 // Split-bf16 form (round 5, SDFA_PREC_BF16X3; BF = true): the same kernel with both contractions on v_mfma_f32_32x32x16_bf16, operands as
 // hi + lo bf16, three products per k-step, smallest first (lo*hi, hi*lo, hi*hi) -- 108 + 108 MFMAs of 32 cycles per tile instead of
-// 264 + 276 of 64.  The basis comes pre-split from the host (api.cpp: pack_pca_bf16) as OCTETS of eight consecutive k per column, the
+// 264 + 276 of 64.  The basis comes pre-split from the host (api_model.cpp: pack_pca_bf16) as OCTETS of eight consecutive k per column, the
 // operand form of the instruction: per triangle block [plane hi | lo][scale rows r = 2 ks + h (12) x 192 | rotat rows (24) x 96]; the
 // slab in LDS keeps the rows that hold real coefficients (11 + 23 per plane, 138 KiB) and ONE shared row of zeros for the all-padding
 // k-groups (k = 88..95 and 184..191).  The coefficient quads are split by the lane that loads them (the lane's frame is its A row).

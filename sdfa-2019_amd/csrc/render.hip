@@ -19,12 +19,12 @@
 //       as dwords (96 bytes per tile row).  No atomics anywhere: the result is independent of scheduling.
 #include "../../include/sdfa_render.h"
 #include "../../include/sdfa_hip.h"
+#include "host.h"
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <vector>
 
@@ -314,8 +314,6 @@ __global__ __launch_bounds__(NT) void render_raster_kernel(RasterArgs a) {
     }
 }
 
-int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
 }  // namespace
 
 struct sdfa_renderer {
@@ -329,20 +327,6 @@ struct sdfa_renderer {
 };
 
 namespace {
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    sdfa_failv(code, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define RENDER_HIP_TRY(expr)                                                                             \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess) return fail(SDFA_EHIP, "%s failed: %s", #expr, hipGetErrorString(e__));   \
-    } while (0)
 
 struct Layout {
     int64_t scr, pos, nrm, box, total;
@@ -359,15 +343,15 @@ Layout layout(const sdfa_renderer *r, int64_t n) {
 }
 
 int check_call(const sdfa_renderer *r, const float *d_verts, int64_t n, void *ws, int64_t ws_bytes, const char *who) {
-    if (!r) return fail(SDFA_EINVAL, "%s: null renderer", who);
-    if (n < 0) return fail(SDFA_EINVAL, "%s: negative frame count", who);
+    if (!r) return sdfa_fail(SDFA_EINVAL, "%s: null renderer", who);
+    if (n < 0) return sdfa_fail(SDFA_EINVAL, "%s: negative frame count", who);
     if (n == 0) return SDFA_OK;
-    if (!d_verts || !ws) return fail(SDFA_EINVAL, "%s: null pointer", who);
-    if (n > 65535) return fail(SDFA_EINVAL, "%s: at most 65535 frames per call (%lld given)", who, (long long)n);
-    if ((uintptr_t)ws & 255) return fail(SDFA_EINVAL, "%s: workspace must be 256-byte aligned", who);
+    if (!d_verts || !ws) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
+    if (n > 65535) return sdfa_fail(SDFA_EINVAL, "%s: at most 65535 frames per call (%lld given)", who, (long long)n);
+    if ((uintptr_t)ws & 255) return sdfa_fail(SDFA_EINVAL, "%s: workspace must be 256-byte aligned", who);
     const int64_t need = layout(r, n).total;
     if (ws_bytes < need)
-        return fail(SDFA_ENOSPACE, "%s: workspace of %lld bytes, %lld needed for %lld frames", who, (long long)ws_bytes, (long long)need, (long long)n);
+        return sdfa_fail(SDFA_ENOSPACE, "%s: workspace of %lld bytes, %lld needed for %lld frames", who, (long long)ws_bytes, (long long)need, (long long)n);
     return SDFA_OK;
 }
 
@@ -376,7 +360,7 @@ int launch_vertex(sdfa_renderer *r, const float *d_verts, int64_t n, int4 *scr, 
     hipLaunchKernelGGL(render_vertex_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_verts, total, (int)r->V,
                        r->normals == SDFA_RENDER_NORMALS_TEMPLATE ? r->d_tmpl_nrm : nullptr, r->d_csr_off, r->d_csr_face,
                        r->d_faces, r->vc, scr, pos, nrm);
-    RENDER_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SDFA_OK;
 }
 
@@ -387,7 +371,7 @@ extern "C" {
 int sdfa_render_abi_version(void) { return SDFA_RENDER_ABI_VERSION; }
 
 int sdfa_render_default_params(sdfa_render_params *out) {
-    if (!out) return fail(SDFA_EINVAL, "render_default_params: null pointer");
+    if (!out) return sdfa_fail(SDFA_EINVAL, "render_default_params: null pointer");
     static const float pose[16] = {
         9.84561989e-01f, -1.14640632e-02f, 1.74657155e-01f, 7.99997887e-02f,
         -2.63421926e-08f, 9.97852584e-01f, 6.54966148e-02f, 3.00000020e-02f,
@@ -409,16 +393,16 @@ sdfa_renderer *sdfa_render_create(const float *h_template_verts, int64_t n_verts
                                   int width, int height, int samples, int normals_mode, const sdfa_render_params *params,
                                   void *stream) {
     if (!h_template_verts || !h_faces || n_verts <= 0 || n_tris <= 0 || n_verts >= (1 << 26) || n_tris >= (1 << 26)) {
-        fail(SDFA_EINVAL, "render_create: null pointer or bad vertex / triangle count");
+        sdfa_fail(SDFA_EINVAL, "render_create: null pointer or bad vertex / triangle count");
         return nullptr;
     }
     if (width < 1 || height < 1 || width > 8192 || height > 8192) {
-        fail(SDFA_EINVAL, "render_create: image size %d x %d outside 1 .. 8192", width, height);
+        sdfa_fail(SDFA_EINVAL, "render_create: image size %d x %d outside 1 .. 8192", width, height);
         return nullptr;
     }
-    if (samples != 1 && samples != 4) { fail(SDFA_EINVAL, "render_create: samples must be 1 or 4 (%d given)", samples); return nullptr; }
+    if (samples != 1 && samples != 4) { sdfa_fail(SDFA_EINVAL, "render_create: samples must be 1 or 4 (%d given)", samples); return nullptr; }
     if (normals_mode != SDFA_RENDER_NORMALS_TEMPLATE && normals_mode != SDFA_RENDER_NORMALS_FRAME) {
-        fail(SDFA_EINVAL, "render_create: unknown normals mode %d", normals_mode);
+        sdfa_fail(SDFA_EINVAL, "render_create: unknown normals mode %d", normals_mode);
         return nullptr;
     }
     sdfa_render_params p;
@@ -427,13 +411,13 @@ sdfa_renderer *sdfa_render_create(const float *h_template_verts, int64_t n_verts
     float vmax = 0.f;
     for (int64_t i = 0; i < 3 * n_verts; ++i) {
         const float a = std::fabs(h_template_verts[i]);
-        if (!std::isfinite(a)) { fail(SDFA_EINVAL, "render_create: non-finite template vertex"); return nullptr; }
+        if (!std::isfinite(a)) { sdfa_fail(SDFA_EINVAL, "render_create: non-finite template vertex"); return nullptr; }
         vmax = a > vmax ? a : vmax;
     }
-    if (vmax == 0.f) { fail(SDFA_EINVAL, "render_create: the template has no extent"); return nullptr; }
+    if (vmax == 0.f) { sdfa_fail(SDFA_EINVAL, "render_create: the template has no extent"); return nullptr; }
     std::vector<int> off(n_verts + 1, 0), face(3 * n_tris);
     for (int64_t i = 0; i < 3 * n_tris; ++i) {
-        if (h_faces[i] >= (uint64_t)n_verts) { fail(SDFA_EINVAL, "render_create: face %lld addresses vertex %u of %lld", (long long)(i / 3), h_faces[i], (long long)n_verts); return nullptr; }
+        if (h_faces[i] >= (uint64_t)n_verts) { sdfa_fail(SDFA_EINVAL, "render_create: face %lld addresses vertex %u of %lld", (long long)(i / 3), h_faces[i], (long long)n_verts); return nullptr; }
         ++off[h_faces[i] + 1];
     }
     for (int64_t v = 0; v < n_verts; ++v) off[v + 1] += off[v];
@@ -473,7 +457,7 @@ sdfa_renderer *sdfa_render_create(const float *h_template_verts, int64_t n_verts
     hipStream_t s = (hipStream_t)stream;
     float *d_tv = nullptr;
     auto bail = [&](const char *what, hipError_t e) {
-        fail(SDFA_EHIP, "render_create: %s failed: %s", what, hipGetErrorString(e));
+        sdfa_fail(SDFA_EHIP, "render_create: %s failed: %s", what, hipGetErrorString(e));
         if (d_tv) (void)hipFree(d_tv);
         sdfa_render_destroy(r);
         return (sdfa_renderer *)nullptr;
@@ -506,7 +490,7 @@ void sdfa_render_destroy(sdfa_renderer *r) {
 }
 
 int64_t sdfa_render_workspace_bytes(const sdfa_renderer *r, int64_t n_frames) {
-    if (!r || n_frames < 0) return fail(SDFA_EINVAL, "render_workspace_bytes: bad argument");
+    if (!r || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "render_workspace_bytes: bad argument");
     return layout(r, n_frames).total;
 }
 
@@ -514,7 +498,7 @@ int sdfa_render_frames(sdfa_renderer *r, const float *d_verts, int64_t n_frames,
                        void *d_workspace, int64_t workspace_bytes, void *stream) {
     int rc = check_call(r, d_verts, n_frames, d_workspace, workspace_bytes, "render_frames");
     if (rc < 0 || n_frames == 0) return rc;
-    if (!d_rgb) return fail(SDFA_EINVAL, "render_frames: null output");
+    if (!d_rgb) return sdfa_fail(SDFA_EINVAL, "render_frames: null output");
     hipStream_t s = (hipStream_t)stream;
     const Layout l = layout(r, n_frames);
     char *ws = (char *)d_workspace;
@@ -525,13 +509,13 @@ int sdfa_render_frames(sdfa_renderer *r, const float *d_verts, int64_t n_frames,
     const int64_t nt = n_frames * r->T;
     hipLaunchKernelGGL(render_setup_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, scr, r->d_faces, nt,
                        (int)r->V, (int)r->T, r->W, r->H, box);
-    RENDER_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     RasterArgs a{scr, pos, nrm, box, r->d_faces, (int)r->V, (int)r->T, r->W, r->H,
                  (r->W % 4 == 0 && ((uintptr_t)d_rgb & 3) == 0) ? 1 : 0, d_rgb, d_tri_ids, r->sc};
     const dim3 grid((unsigned)((r->W + TILE - 1) / TILE), (unsigned)((r->H + TILE - 1) / TILE), (unsigned)n_frames);
     if (r->samples == 4) hipLaunchKernelGGL(render_raster_kernel<4>, grid, dim3(NT), 0, s, a);
     else hipLaunchKernelGGL(render_raster_kernel<1>, grid, dim3(NT), 0, s, a);
-    RENDER_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SDFA_OK;
 }
 
@@ -539,7 +523,7 @@ int sdfa_render_debug_screen(sdfa_renderer *r, const float *d_verts, int64_t n_f
                              void *d_workspace, int64_t workspace_bytes, void *stream) {
     int rc = check_call(r, d_verts, n_frames, d_workspace, workspace_bytes, "render_debug_screen");
     if (rc < 0 || n_frames == 0) return rc;
-    if (!d_screen) return fail(SDFA_EINVAL, "render_debug_screen: null output");
+    if (!d_screen) return sdfa_fail(SDFA_EINVAL, "render_debug_screen: null output");
     const Layout l = layout(r, n_frames);
     char *ws = (char *)d_workspace;
     return launch_vertex(r, d_verts, n_frames, (int4 *)d_screen, (float4 *)(ws + l.pos), (float4 *)(ws + l.nrm), (hipStream_t)stream);

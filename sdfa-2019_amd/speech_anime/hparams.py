@@ -92,7 +92,7 @@ def configure(args):
     return _wrap(hp)
 
 
-# Front-end and frame-geometry values the kernels and sdfa_frame_index are built for (csrc/api.cpp build_frontend,
+# Front-end and frame-geometry values the kernels and sdfa_frame_index are built for (csrc/api_frontend.cpp build_frontend,
 # csrc/frontend.hip, sdfa_amd/engine.py).  A checkpoint's hparams.json that disagrees would run without error and give
 # wrong timestamps / features, so it is refused by name instead.
 _COMPILED_IN = {

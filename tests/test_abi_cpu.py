@@ -59,6 +59,33 @@ def test_overlong_clip_is_refused_on_the_host():
         engine.frame_index(2 ** 29, 16000)
 
 
+def test_option_table_of_the_header_is_what_the_library_accepts():
+    """The comment table next to sdfa_debug_set_option in include/sdfa_hip.h is the specification of the A/B options: the library
+    accepts every name it documents (and no retired or unknown one) and enforces the documented ranges of the stream options."""
+    hdr = open(os.path.join(ROOT, "include", "sdfa_hip.h")).read()
+    comment = hdr[:hdr.index("int sdfa_debug_set_option(")].rsplit("/*", 1)[1]
+    names = []
+    for row in re.findall(r'^ \*   ("[a-z0-9_]+"(?: / "[a-z0-9_]+")*)', comment, flags=re.M):
+        names += re.findall(r'"([a-z0-9_]+)"', row)
+    assert len(names) == len(set(names)) >= 18, names
+    set_option, last_error = _lib.lib.sdfa_debug_set_option, _lib.lib.sdfa_last_error
+    try:
+        for name in names:
+            assert set_option(name.encode(), 0) == _lib.OK, (name, last_error())
+        for name in ("pca_unfused", "conv_unfused", "no_such_option"):
+            assert set_option(name.encode(), 0) == _lib.EINVAL, name
+            assert b"unknown option" in last_error(), (name, last_error())
+        refused = [("frontend_stream_block", 257), ("frontend_stream_block", -1), ("frontend_stream_slots", 257),
+                   ("frontend_stream_slots", -1), ("frontend_stream_spin_max", -1)]
+        for name, value in refused:
+            assert name in names
+            assert set_option(name.encode(), value) == _lib.EINVAL, (name, value)
+            assert last_error().startswith(name.encode() + b": 0 (default) or "), (name, value, last_error())
+    finally:
+        for name in names:
+            set_option(name.encode(), 0)
+
+
 def test_short_clip_raises_like_reference():
     with pytest.raises(AssertionError):
         engine.frame_index(2400, 8000)
