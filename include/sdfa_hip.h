@@ -206,15 +206,20 @@ int64_t sdfa_workspace_status(const void *d_workspace, int word, void *stream);
  *   d_z           out [n_frames][512]   attention context (z_audio)
  *   d_align       out [n_frames][64]    attention weights (align_dict["audio_encoder10"]); may be NULL
  * Alignment: d_audio_feat, d_z and d_workspace 16 bytes, d_align 4 bytes (SDFA_EINVAL otherwise).
+ *
+ * The per-column stages (conv stack, frequency LSTM, its projection, the layer-0 input projection) are evaluated once per
+ * DISTINCT column: overlapping analysis windows hold bit-identical columns, and the call finds them in d_audio_feat itself, per
+ * workspace chunk, on every call -- a 64-bit hash per column proposes pairs among the 64 preceding frames, and a pair is shared
+ * only after its 384 words have been compared in full as bit patterns.  The rows are bitwise those of evaluating every column
+ * ("encoder_dedup_off" = 1 does that; sdfa_debug_keep_intermediates models always do).  Features without copies cost the scan only.
  * ---------------------------------------------------------------------------------------- */
 int sdfa_encoder_forward(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames,
                          float *d_z, float *d_align, void *d_workspace, int64_t workspace_bytes,
                          void *stream);
 
-/* Same result, fewer evaluations ("legal redundancy"): the per-column stages (conv stack,
- * frequency LSTM, its projection) are run once per DISTINCT column.  Windows of one clip whose starts differ by
- * a whole number of hops contain bit-identical interior columns (t in [6,58]); the library finds them on the device
- * from the frame table of sdfa_frame_index / sdfa_mel_frontend, on every call.
+/* The same sharing ("legal redundancy") from the frame table instead of a scan of the features: windows of one
+ * clip whose starts differ by a whole number of hops contain bit-identical interior columns (t in [6,58]); the library builds the
+ * map on the device from the frame table of sdfa_frame_index / sdfa_mel_frontend, on every call, and reads no feature to do so.
  *   d_frame_clip  [n_frames] int32 clip id        d_frame_start [n_frames] int64 window start in its clip
  *   hop           STFT hop in samples (int(0.008*sr))
  * audio_feat must be what sdfa_mel_frontend produced for exactly this frame table. */
@@ -303,6 +308,9 @@ int sdfa_ensemble_mean(const float *d_a, const float *d_b, int64_t n, float *d_o
  *                      hop by hop (same features, bit for bit; only the order of the mel table's rows differs)
  *   "share_gx0_off"    1 = sdfa_encoder_forward_shared expands the frequency projection to all columns before the layer-0 BiLSTM input
  *                      projection (rounds 2-3) instead of projecting the distinct columns and letting the recurrence read them through the map
+ *   "encoder_dedup_off" 1 = sdfa_encoder_forward (no frame table) evaluates every column of every frame, as it did before it learnt to find the
+ *                      identical columns of audio_feat itself (hash, then a full bit-pattern compare of every proposed pair, on the device, on
+ *                      every call); the every-column path is the reference the sharing tests compare against.  Same bits
  *   "conv_fp32"        1 = the body precision modes (bf16, bf16x3, bf16x6) keep the conv stack on the fp32 kernel instead of
  *                      conv123_bf16_kernel (NOT bit-identical: that stack's operand rounding)
  *   "pca_fp32"         1 = SDFA_PREC_BF16X3 keeps the dgrad PCA expansion on the fp32 kernel (NOT bit-identical: the expansion's operand rounding)
@@ -323,8 +331,9 @@ int sdfa_ensemble_mean(const float *d_a, const float *d_b, int64_t n, float *d_o
  *                      and workgroups per block (0 = 12); same bits for every value   */
 int sdfa_debug_set_option(const char *name, int value);
 int sdfa_debug_keep_intermediates(sdfa_model *m, int on);   /* un-aliased workspace: call before sizing it */
-/* Number of distinct columns the LAST sdfa_encoder_forward_shared call evaluated for a chunk of n_frames frames
- * (synchronises the stream).  Tests / reporting only. */
+/* Number of distinct columns the LAST sdfa_encoder_forward / sdfa_encoder_forward_shared call evaluated for a chunk of n_frames
+ * frames (synchronises the stream; a call that evaluated every column -- "encoder_dedup_off", kept intermediates -- leaves the
+ * count of the call before it).  Tests / reporting only. */
 int64_t sdfa_debug_distinct_columns(const sdfa_model *m, int64_t n_frames, const void *d_workspace, void *stream);
 int sdfa_debug_tap(const sdfa_model *m, int what, int64_t n_frames, float *d_dst, const void *d_workspace,
                    void *stream);

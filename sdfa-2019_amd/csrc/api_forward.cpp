@@ -7,7 +7,7 @@
 #include <algorithm>
 
 // A/B options this file reads (api_core.cpp)
-extern thread_local int g_sdfa_freq_lstm_shape, g_sdfa_pca_lds, g_sdfa_pca_fp32, g_sdfa_conv_fp32, g_sdfa_share_gx0_off, g_sdfa_attn_unfused;
+extern thread_local int g_sdfa_freq_lstm_shape, g_sdfa_pca_lds, g_sdfa_pca_fp32, g_sdfa_conv_fp32, g_sdfa_share_gx0_off, g_sdfa_attn_unfused, g_sdfa_encoder_dedup_off;
 
 // ================================================================================================
 // workspace layout (floats), per chunk of Nc frames, Mc = 64*Nc columns
@@ -179,20 +179,34 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         ca.w1 = m->w1; ca.b1 = m->b1; ca.s1 = m->s1; ca.t1 = m->t1; ca.P1 = ws + w.P1;
         ca.w2 = m->w2; ca.b2 = m->b2; ca.s2 = m->s2; ca.t2 = m->t2;
         ca.w3 = m->w3; ca.b3 = m->b3; ca.s3 = m->s3; ca.t3 = m->t3; ca.X3 = ws + w.X3;
-        const bool share = d_frame_clip != nullptr;
+        // Column sharing (share.hip): with the frame table, the map comes from the table.  Without one it comes from the features
+        // themselves -- every link compared in full on the device, per chunk, on every call -- unless the debug taps are on (they read
+        // the every-column layout) or "encoder_dedup_off" asks for the every-column path.
+        const bool table = d_frame_clip != nullptr;
+        const bool share = table || (!m->keep && !g_sdfa_encoder_dedup_off);
         const int64_t *d_ulimit = nullptr;     // device scalar: number of distinct columns, padded to 256
         int32_t *col_to_u = nullptr;
         if (share) {
             int32_t *sh = reinterpret_cast<int32_t *>(ws + w.SH);
             ShareArgs sa{};
-            sa.frame_clip = d_frame_clip + f0; sa.frame_start = d_frame_start + f0; sa.hop = hop;
-            sa.t_lo = 6; sa.t_hi = 58;      // feature columns: see share.hip
             sa.N = N; sa.Nc = Nc; sa.Mc = Mc;
             sa.counts = reinterpret_cast<int64_t *>(sh);           // 16 ints reserved
             sa.prev = sh + 16; sa.shift = sa.prev + Nc;
             sa.owner = sa.shift + Nc; sa.flag = sa.owner + Mc; sa.uid = sa.flag + Mc;
             sa.col_src = sa.uid + Mc; sa.col_to_u = sa.col_src + Mc; sa.tile_sum = sa.col_to_u + Mc;
-            pf.begin("share_map"); HIP_TRY(sdfa_launch_share_map(sa, s)); pf.end();
+            pf.begin("share_map");
+            if (table) {
+                sa.frame_clip = d_frame_clip + f0; sa.frame_start = d_frame_start + f0; sa.hop = hop;
+                sa.t_lo = 6; sa.t_hi = 58;      // feature columns: see share.hip
+                HIP_TRY(sdfa_launch_share_map(sa, s));
+            } else {
+                // scratch of the scan (2 Mc + 2 Nc words): the head of the frequency LSTM's hidden-state region, which nobody has written
+                // yet in this chunk (the conv stack writes X3; the frequency LSTM is HF's first writer) and which is 8192 Mc words long
+                sa.feat = ca.audio_feat;
+                sa.hash = reinterpret_cast<uint64_t *>(ws + w.HF); sa.linked = sa.hash + Mc;
+                HIP_TRY(sdfa_launch_share_map_content(sa, s));
+            }
+            pf.end();
             d_ulimit = sa.counts + 1; col_to_u = sa.col_to_u;
             ca.col_src = sa.col_src; ca.col_limit = d_ulimit;
         }

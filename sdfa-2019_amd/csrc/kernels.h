@@ -205,8 +205,13 @@ struct ShareArgs {
     int32_t *col_src;            // [Mc] out: audio_feat row of each distinct column (-1 padding)
     int32_t *col_to_u;           // [Mc] out: distinct-column index of every column, in the index order above
     int64_t *counts;             // [2]  out: number of distinct columns, and that rounded up to 256
+    // sdfa_launch_share_map_content only (no frame table: prev / shift come from the features themselves)
+    const float *feat;           // [N * 64][384] the chunk's audio_feat, one row per column
+    uint64_t *hash;              // [N * 64] scratch: 64-bit hash of each column's bit pattern, frame-major
+    uint64_t *linked;            // [N] scratch: bit t = column t of frame n has been compared in full with column t + shift[n] of frame prev[n], and is equal
 };
 hipError_t sdfa_launch_share_map(const ShareArgs &a, hipStream_t s);
+hipError_t sdfa_launch_share_map_content(const ShareArgs &a, hipStream_t s);   // the same map, built from the contents of audio_feat (t_lo / t_hi / frame_clip / frame_start / hop unused)
 hipError_t sdfa_launch_share_prev(const ShareArgs &a, hipStream_t s);     // prev / shift only (the spectral-stream front end reads the chains from them)
 hipError_t sdfa_launch_expand_cols(const float *Zu, const int32_t *col_to_u, float *Z, int nquads, int64_t Mc, hipStream_t s);
 
