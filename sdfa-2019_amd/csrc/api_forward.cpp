@@ -17,7 +17,9 @@ namespace {
 constexpr int64_t CT_WORDS = 2048, CT_FLAGS = 16, ST_WORDS = SDFA_WS_STATUS_BYTES / 4;
 
 struct Ws {
-    int64_t P1, X3, HF, Z, GX, H0, H1, KP, QC, QP, ZK, R, SH, ZU, CT, total;   // offsets in floats
+    int64_t P1, X3, HF, Z, GX, H0, H1, KP, QC, QP, ZK, SH, ZU, total;   // offsets in floats
+    int64_t TRUNK, A0, A1, COEF;        // regressor scratch: K4 slabs of Nc columns
+    int64_t CT_FREQ, CT_PCA, CT_FLAG;   // control words (ints)
 };
 
 Ws layout(int64_t Nc, bool keep) {
@@ -37,11 +39,13 @@ Ws layout(int64_t Nc, bool keep) {
         w.X3 = B; w.Z = B; w.H0 = B + 256 * Mc; w.H1 = B + 768 * Mc; w.KP = B + 1280 * Mc;
     }
     w.QC = take(512 * Nc); w.QP = take(128 * Nc); w.ZK = take(512 * Nc);
-    w.R = take(2560 * Nc);   // regressor scratch: trunk 512 | a 512 | b 256 | coef 288 (+ second branch a/b)
-    w.SH = take(2 * Nc + 5 * Mc + Mc / 1024 + 128);   // column-sharing tables (int32 / int64 counters)
+    const int64_t R = take(2560 * Nc);   // regressor scratch: trunk 512 rows | a 512 | b 256 | coef up to 288 (the branches of the dgrad head share a / b)
+    w.TRUNK = R; w.A0 = R + 512 * Nc; w.A1 = R + 1024 * Nc; w.COEF = R + 1280 * Nc;
+    w.SH = take(sdfa_share_table_words(Nc) + 111);   // column-sharing tables (int32 / int64 counters), with the slack they have always had
     w.ZU = keep ? take(256 * Mc) : w.P1; // freq-proj output over distinct columns (pool1 is dead by then)
-    w.CT = take(CT_WORDS);               // ints: [0] / [1] work-queue heads of the persistent kernels; [16 ..] the flag block of
-                                         // time_lstm_split_kernel (timeout word + one flag per workgroup, at most 4 per CU-sized grid)
+    const int64_t CT = take(CT_WORDS);   // ints: [0] / [1] work-queue heads of the persistent kernels (frequency LSTM / PCA expansion); [16 ..] the flag
+                                         // block of time_lstm_split_kernel (timeout word + one flag per workgroup, at most 4 per CU-sized grid)
+    w.CT_FREQ = CT; w.CT_PCA = CT + 1; w.CT_FLAG = CT + CT_FLAGS;
     w.total = o;
     return w;
 }
@@ -74,10 +78,9 @@ struct Prof {
 };
 
 GemmArgs gemm_fc(const sdfa_model::Fc &fc, const float *Q, int64_t ldq, float *D, int64_t Nc, const int64_t *spk, int64_t nreal) {
-    GemmArgs g{};
-    g.P = fc.w; g.Q = Q; g.D = D; g.bias = fc.b; g.cond_w = fc.cw; g.cond_idx = fc.cw ? spk : nullptr;
-    g.ldp = fc.Ppad; g.ldq = ldq; g.ldd = Nc; g.Ppad = fc.Ppad; g.Qpad = Nc; g.Pstore = fc.Pstore; g.Qreal = nreal;
-    g.K = fc.K; g.seg_k = fc.K; g.seg_col = 0; g.act = fc.act; g.out_mode = OUT_K4; g.bias_on_q = 0;
+    GemmArgs g = sdfa_gemm_k4(fc.w, fc.Ppad, Q, ldq, D, Nc, fc.K);
+    g.bias = fc.b; g.cond_w = fc.cw; g.cond_idx = fc.cw ? spk : nullptr;
+    g.Pstore = fc.Pstore; g.Qreal = nreal; g.act = fc.act;
     return g;
 }
 
@@ -187,13 +190,9 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         const int64_t *d_ulimit = nullptr;     // device scalar: number of distinct columns, padded to 256
         int32_t *col_to_u = nullptr;
         if (share) {
-            int32_t *sh = reinterpret_cast<int32_t *>(ws + w.SH);
             ShareArgs sa{};
             sa.N = N; sa.Nc = Nc; sa.Mc = Mc;
-            sa.counts = reinterpret_cast<int64_t *>(sh);           // 16 ints reserved
-            sa.prev = sh + 16; sa.shift = sa.prev + Nc;
-            sa.owner = sa.shift + Nc; sa.flag = sa.owner + Mc; sa.uid = sa.flag + Mc;
-            sa.col_src = sa.uid + Mc; sa.col_to_u = sa.col_src + Mc; sa.tile_sum = sa.col_to_u + Mc;
+            sdfa_share_carve(sa, reinterpret_cast<int32_t *>(ws + w.SH));
             pf.begin("share_map");
             if (table) {
                 sa.frame_clip = d_frame_clip + f0; sa.frame_start = d_frame_start + f0; sa.hop = hop;
@@ -228,14 +227,12 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         // launch form: the "freq_lstm_shape" option if set; else, for the fp32 kernel, what sdfa_model_autotune measured (the split-bf16
         // kernels have their own default: the autotuned fp32 form says nothing about them)
         const int fl_terms = stage_terms(m, STAGE_BODY);
-        FreqLstmArgs fa{ws + w.X3, m->fl_w, m->fl_b, ws + w.HF, Mc, d_ulimit, m->fl_wb, fl_terms, reinterpret_cast<int *>(ws + w.CT),
+        FreqLstmArgs fa{ws + w.X3, m->fl_w, m->fl_b, ws + w.HF, Mc, d_ulimit, m->fl_wb, fl_terms, reinterpret_cast<int *>(ws + w.CT_FREQ),
                         g_sdfa_freq_lstm_shape ? g_sdfa_freq_lstm_shape : (fl_terms ? 0 : m->freq_shape.load()), m->reserved_cus.load()};
         pf.begin("freq_lstm"); HIP_TRY(sdfa_launch_freq_lstm(fa, s)); pf.end();
 
-        GemmArgs g{};   // FreqLstm._proj: Linear(8192 -> 256) + bias
-        g.P = m->fp_w; g.Q = ws + w.HF; g.D = ws + w.Z; g.bias = m->fp_b;
-        g.ldp = 256; g.ldq = Mc; g.ldd = Mc; g.Ppad = 256; g.Qpad = Mc; g.Pstore = 256; g.Qreal = Mc;
-        g.K = 8192; g.seg_k = 8192; g.act = ACT_NONE; g.out_mode = OUT_K4; g.q_tile_major = 1; g.q_slab_rows = HF_SLAB_ROWS;
+        GemmArgs g = sdfa_gemm_k4(m->fp_w, 256, ws + w.HF, Mc, ws + w.Z, Mc, 8192);   // FreqLstm._proj: Linear(8192 -> 256) + bias
+        g.bias = m->fp_b; g.q_tile_major = 1; g.q_slab_rows = HF_SLAB_ROWS;
         g.terms = stage_terms(m, STAGE_BODY);
         g.reserve_cus = m->reserved_cus.load();
         if (share) { g.D = ws + w.ZU; g.q_limit = d_ulimit; }
@@ -256,16 +253,13 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         for (int l = 0; l < 2; ++l) {
             const bool mapped = share_gx0 && l == 0;
             float *gx = mapped ? ws + w.HF : ws + w.GX;
-            GemmArgs gi{};
-            gi.P = m->gx_w[l]; gi.Q = xin; gi.D = gx;
-            gi.ldp = 2048; gi.ldq = Mc; gi.ldd = Mc; gi.Ppad = 2048; gi.Qpad = Mc; gi.Pstore = 2048; gi.Qreal = Mc;
-            gi.K = l == 0 ? 256 : 512; gi.seg_k = gi.K; gi.act = ACT_NONE; gi.out_mode = OUT_K4;
+            GemmArgs gi = sdfa_gemm_k4(m->gx_w[l], 2048, xin, Mc, gx, Mc, l == 0 ? 256 : 512);
             gi.terms = stage_terms(m, STAGE_BODY);
             gi.reserve_cus = m->reserved_cus.load();
             if (mapped) gi.q_limit = d_ulimit;
             pf.begin(gxn[l]); HIP_TRY(sdfa_launch_gemm(gi, s)); pf.end();
             TimeLstmArgs ta{gx, m->tl_w[l], hout[l], Nc, Mc, m->tl_wb[l], stage_terms(m, STAGE_BODY),
-                            reinterpret_cast<unsigned *>(ws + w.CT) + CT_FLAGS, CT_WORDS - CT_FLAGS, m->tl_w16[l],
+                            reinterpret_cast<unsigned *>(ws + w.CT_FLAG), CT_WORDS - CT_FLAGS, m->tl_w16[l],
                             reinterpret_cast<unsigned *>(ws), m->reserved_cus.load(), mapped ? col_to_u : nullptr};
             pf.begin(lsn[l]); HIP_TRY(sdfa_launch_time_lstm(ta, s)); pf.end();
             xin = hout[l];
@@ -279,20 +273,14 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         // mode (fp32-equivalent products) takes the exact fp32 pass too: faster than six bf16 products through a GEMM, and exact.
         const bool key_fused = g_sdfa_attn_unfused != 1;
         pf.begin("attn_proj");
-        GemmArgs gk{};
-        gk.P = m->kp_w; gk.Q = ws + w.H1; gk.D = ws + w.KP;
-        gk.ldp = 128; gk.ldq = Mc; gk.ldd = Mc; gk.Ppad = 128; gk.Qpad = Mc; gk.Pstore = 128; gk.Qreal = Mc;
-        gk.K = 512; gk.seg_k = 512; gk.act = ACT_NONE; gk.out_mode = OUT_K4; gk.terms = at_terms;
+        GemmArgs gk = sdfa_gemm_k4(m->kp_w, 128, ws + w.H1, Mc, ws + w.KP, Mc, 512);
+        gk.terms = at_terms;
         if (!key_fused) HIP_TRY(sdfa_launch_gemm(gk, s));
-        GemmArgs gc{};
-        gc.P = m->qc_w; gc.Q = ws + w.H1 + 31 * Nc * 4; gc.D = ws + w.QC;
-        gc.ldp = 512; gc.ldq = Mc; gc.ldd = Nc; gc.Ppad = 512; gc.Qpad = Nc; gc.Pstore = 512; gc.Qreal = Nc;
-        gc.K = 1536; gc.seg_k = 512; gc.seg_col = Nc; gc.act = ACT_NONE; gc.out_mode = OUT_K4; gc.terms = gk.terms;
+        GemmArgs gc = sdfa_gemm_k4(m->qc_w, 512, ws + w.H1 + 31 * Nc * 4, Mc, ws + w.QC, Nc, 1536);   // Nc output columns read out of H1's Mc
+        gc.seg_k = 512; gc.seg_col = Nc; gc.terms = at_terms;                                        // three taps: time steps 31, 32, 33
         HIP_TRY(sdfa_launch_gemm(gc, s));
-        GemmArgs gq{};
-        gq.P = m->qp_w; gq.Q = ws + w.QC; gq.D = ws + w.QP;
-        gq.ldp = 128; gq.ldq = Nc; gq.ldd = Nc; gq.Ppad = 128; gq.Qpad = Nc; gq.Pstore = 128; gq.Qreal = Nc;
-        gq.K = 512; gq.seg_k = 512; gq.act = ACT_NONE; gq.out_mode = OUT_K4; gq.terms = gk.terms;
+        GemmArgs gq = sdfa_gemm_k4(m->qp_w, 128, ws + w.QC, Nc, ws + w.QP, Nc, 512);
+        gq.terms = at_terms;
         HIP_TRY(sdfa_launch_gemm(gq, s));
         // exact fp32, large chunks: the whole layer in ONE pass over H (running softmax + context while the tile is in LDS: attn_fused_f32_kernel);
         // "attn_unfused" = 2 keeps the two-kernel form
@@ -339,7 +327,7 @@ int sdfa_model_autotune(sdfa_model *m, int64_t n_frames, void *d_workspace, int6
     float best_ms = 0.f;
     int best = m->freq_shape.load(), rc = SDFA_OK;
     for (int form : forms) {
-        FreqLstmArgs fa{ws + w.X3, m->fl_w, m->fl_b, ws + w.HF, Mc, nullptr, m->fl_wb, 0, reinterpret_cast<int *>(ws + w.CT), form, m->reserved_cus.load()};
+        FreqLstmArgs fa{ws + w.X3, m->fl_w, m->fl_b, ws + w.HF, Mc, nullptr, m->fl_wb, 0, reinterpret_cast<int *>(ws + w.CT_FREQ), form, m->reserved_cus.load()};
         float ms = 0.f;
         for (int rep = 0; rep < 3 && rc == SDFA_OK; ++rep) {      // one warm launch, two timed
             if (rep == 1 && hipEventRecord(e0, s) != hipSuccess) rc = SDFA_EHIP;
@@ -444,8 +432,7 @@ int sdfa_regress_forward_multi(const sdfa_model *m, const float *d_z, const int6
         const int64_t N = std::min(cap, n_frames - f0);
         const int64_t Nc = round_up(N, 128);
         const Ws w = layout(Nc, m->keep);
-        float *zk = ws + w.ZK, *r = ws + w.R;
-        float *trunk = r, *a0 = r + 512 * Nc, *a1 = r + 1024 * Nc, *coef = r + 1280 * Nc;   // coef: up to 288 rows
+        float *zk = ws + w.ZK, *trunk = ws + w.TRUNK, *a0 = ws + w.A0, *a1 = ws + w.A1, *coef = ws + w.COEF;
         const int64_t *spk = d_speaker_id + f0;
         pf.begin("mlp");
         HIP_TRY(sdfa_launch_rows_to_k4(d_z + f0 * 512, N, 512, zk, Nc, s));
@@ -469,7 +456,7 @@ int sdfa_regress_forward_multi(const sdfa_model *m, const float *d_z, const int6
         pf.end();
         if (d_out) {
             pf.begin("pca");
-            HIP_TRY(expand_rows(m, coef, N, Nc, f0, h_d_outs, n_outs, reinterpret_cast<int *>(ws + w.CT) + 1, s));
+            HIP_TRY(expand_rows(m, coef, N, Nc, f0, h_d_outs, n_outs, reinterpret_cast<int *>(ws + w.CT_PCA), s));
             pf.end();
         }
     }
@@ -493,7 +480,7 @@ int sdfa_expand_coef(const sdfa_model *m, const float *d_coef, int64_t n_frames,
         const int64_t N = std::min(cap, n_frames - f0);
         const int64_t Nc = round_up(N, 128);
         const Ws w = layout(Nc, m->keep);
-        float *coef = ws + w.R + 1280 * Nc;                  // the regressor's coefficient slab: same place, same layout
+        float *coef = ws + w.COEF;                           // the regressor's coefficient slab
         const float *src = d_coef + f0 * m->coef_dim;
         pf.begin("pca");
         if (m->head == SDFA_HEAD_DGRAD) {
@@ -503,7 +490,7 @@ int sdfa_expand_coef(const sdfa_model *m, const float *d_coef, int64_t n_frames,
             HIP_TRY(sdfa_launch_rows_seg_to_k4(src, m->coef_dim, N, 0, SDFA_COEF_OFFSETS, coef, Nc, 0, 64, s));
         }
         float *outs[1] = {d_out};
-        HIP_TRY(expand_rows(m, coef, N, Nc, f0, outs, 1, reinterpret_cast<int *>(ws + w.CT) + 1, s));
+        HIP_TRY(expand_rows(m, coef, N, Nc, f0, outs, 1, reinterpret_cast<int *>(ws + w.CT_PCA), s));
         pf.end();
     }
     return SDFA_OK;

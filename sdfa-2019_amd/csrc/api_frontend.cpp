@@ -100,6 +100,23 @@ int build_frontend(int sr, FrontendCache &fc) {
     return SDFA_OK;
 }
 
+// The constants of `sample_rate` on the current device: built on first use, then cached.
+int frontend_consts(int sample_rate, FrontendConsts &c) {
+    std::lock_guard<std::mutex> lk(g_fe_mu);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    auto key = sample_rate * 64 + dev;
+    auto it = g_fe.find(key);
+    if (it == g_fe.end()) {
+        FrontendCache fc;
+        int rc = build_frontend(sample_rate, fc);
+        if (rc) return rc;
+        it = g_fe.emplace(key, fc).first;
+    }
+    c = it->second.c;
+    return SDFA_OK;
+}
+
 // Frame idx + 1 of sdfa_frame_index, a function of idx alone (the loop there counts idx up from -1.0 in exact steps of 1.0).
 struct FramePos { float fs; int64_t s, e; int32_t ts; };
 FramePos frame_pos(double idx, int sample_rate, int fps, int64_t sliding, int ts_delta_ms) {
@@ -158,20 +175,7 @@ int sdfa_mel_frontend(const float *d_pcm, const int64_t *d_clip_off, const int64
     if (!d_pcm || !d_clip_off || !d_clip_len || !d_frame_clip || !d_frame_start || !d_audio_feat || n_clips <= 0 || n_frames < 0)
         return sdfa_fail(SDFA_EINVAL, "mel_frontend: null pointer or bad count");
     FrontendConsts c;
-    {
-        std::lock_guard<std::mutex> lk(g_fe_mu);
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        auto key = sample_rate * 64 + dev;
-        auto it = g_fe.find(key);
-        if (it == g_fe.end()) {
-            FrontendCache fc;
-            int rc = build_frontend(sample_rate, fc);
-            if (rc) return rc;
-            it = g_fe.emplace(key, fc).first;
-        }
-        c = it->second.c;
-    }
+    if (int rc = frontend_consts(sample_rate, c)) return rc;
     HIP_TRY(sdfa_launch_frontend(c, d_pcm, d_clip_off, d_clip_len, d_frame_clip, d_frame_start, n_frames, d_audio_feat,
                                  (hipStream_t)stream));
     return SDFA_OK;
@@ -186,7 +190,7 @@ struct FeWs { int64_t Nc, Mc, map_ints, table_off, total; };
 FeWs fe_layout(int64_t n_frames) {
     FeWs w;
     w.Nc = round_up(n_frames, 128); w.Mc = 64 * w.Nc;
-    w.map_ints = round_up(16 + 2 * w.Nc + 5 * w.Mc + w.Mc / 1024 + 2, 64);
+    w.map_ints = round_up(sdfa_share_table_words(w.Nc) + 1, 64);
     w.table_off = w.map_ints * 4;
     w.total = w.table_off + w.Mc * 128 * 4;
     return w;
@@ -222,20 +226,7 @@ int sdfa_mel_frontend_gather(const float *d_pcm, const int64_t *d_clip_off, cons
                     (long long)w.total, (long long)n_frames);
     if (w.Mc >= (int64_t)1 << 31) return sdfa_fail(SDFA_EINVAL, "mel_frontend_gather: too many frames in one call");
     FrontendConsts c;
-    {
-        std::lock_guard<std::mutex> lk(g_fe_mu);
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        auto key = sample_rate * 64 + dev;
-        auto it = g_fe.find(key);
-        if (it == g_fe.end()) {
-            FrontendCache fc;
-            int rc = build_frontend(sample_rate, fc);
-            if (rc) return rc;
-            it = g_fe.emplace(key, fc).first;
-        }
-        c = it->second.c;
-    }
+    if (int rc = frontend_consts(sample_rate, c)) return rc;
     hipStream_t s = (hipStream_t)stream;
     int32_t *sh = reinterpret_cast<int32_t *>(d_workspace);
     ShareArgs sa{};
@@ -243,10 +234,7 @@ int sdfa_mel_frontend_gather(const float *d_pcm, const int64_t *d_clip_off, cons
     sa.t_lo = 1; sa.t_hi = 63;          // every window column but the first (raw first sample) is a function of (clip, position)
     sa.frame_major = g_sdfa_frontend_t_major ? 0 : 1;      // distinct columns numbered clip by clip, hop by hop, per-column arrays indexed [n][t] (share.hip: col_index)
     sa.N = n_frames; sa.Nc = w.Nc; sa.Mc = w.Mc;
-    sa.counts = reinterpret_cast<int64_t *>(sh);
-    sa.prev = sh + 16; sa.shift = sa.prev + w.Nc;
-    sa.owner = sa.shift + w.Nc; sa.flag = sa.owner + w.Mc; sa.uid = sa.flag + w.Mc;
-    sa.col_src = sa.uid + w.Mc; sa.col_to_u = sa.col_src + w.Mc; sa.tile_sum = sa.col_to_u + w.Mc;
+    sdfa_share_carve(sa, sh);
     // sh[8]: the stream kernel's status word (bounded hand-off waits that expired -- never, unless its logic is wrong -- and were
     // repaired by the pass behind the kernel).  Zeroed by EVERY call, whichever form runs, so that sdfa_debug_frontend_status never
     // reads a stale or uninitialised word after a two-kernel / radix-4 / t-major call or on a fresh workspace.
@@ -323,20 +311,7 @@ int sdfa_mel_frontend_ring(const float *d_rings, int r, int32_t n_rings, const i
                     (long long)w.total, (long long)n_frames);
     if (w.Mc >= (int64_t)1 << 31) return sdfa_fail(SDFA_EINVAL, "mel_frontend_ring: too many frames in one call");
     FrontendConsts c;
-    {
-        std::lock_guard<std::mutex> lk(g_fe_mu);
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        auto key = sample_rate * 64 + dev;
-        auto it = g_fe.find(key);
-        if (it == g_fe.end()) {
-            FrontendCache fc;
-            int rc = build_frontend(sample_rate, fc);
-            if (rc) return rc;
-            it = g_fe.emplace(key, fc).first;
-        }
-        c = it->second.c;
-    }
+    if (int rc = frontend_consts(sample_rate, c)) return rc;
     if (r < 1 || r > 28 || ((int64_t)1 << r) < (int64_t)c.hop * 63 + c.win)
         return sdfa_fail(SDFA_EINVAL, "mel_frontend_ring: rings of 2^%d samples cannot hold a window of %d samples (r <= 28)", r, c.hop * 63 + c.win);
     hipStream_t s = (hipStream_t)stream;
@@ -346,8 +321,7 @@ int sdfa_mel_frontend_ring(const float *d_rings, int r, int32_t n_rings, const i
     sa.t_lo = 1; sa.t_hi = 63;
     sa.frame_major = 1;
     sa.N = n_frames; sa.Nc = w.Nc; sa.Mc = w.Mc;
-    sa.counts = reinterpret_cast<int64_t *>(sh);
-    sa.prev = sh + 16; sa.shift = sa.prev + w.Nc;
+    sdfa_share_carve(sa, sh);      // only prev / shift are used
     HIP_TRY(hipMemsetAsync(sh + 8, 0, sizeof(int32_t), s));      // the status word, as sdfa_mel_frontend_gather
     HIP_TRY(sdfa_launch_share_prev(sa, s));
     HIP_TRY(sdfa_launch_mel_ring(c, d_rings, r, n_rings, d_view_ring, d_view_hi, d_frame_view, d_frame_start, sa.prev, sa.shift, n_frames,

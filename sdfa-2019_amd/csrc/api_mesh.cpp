@@ -205,10 +205,7 @@ static int mesh_solve(const sdfa_mesh *m, const float *d_dgrad, const int64_t *d
     a.rhs = rhs; a.sol = sol; a.verts = d_verts; a.ld = ld;
     HIP_TRY(hipMemsetAsync(rhs, 0, (size_t)m->free_pad * ld * 4, s));   // padding columns / rows feed the GEMM
     HIP_TRY(sdfa_launch_mesh_rhs(a, s));
-    GemmArgs g{};
-    g.P = m->inv_k4; g.Q = rhs; g.D = sol;
-    g.ldp = m->free_pad; g.ldq = ld; g.ldd = ld; g.Ppad = m->free_pad; g.Qpad = ld; g.Pstore = m->free_pad; g.Qreal = ld;
-    g.K = m->free_pad; g.seg_k = g.K; g.act = ACT_NONE; g.out_mode = OUT_K4;
+    const GemmArgs g = sdfa_gemm_k4(m->inv_k4, m->free_pad, rhs, ld, sol, ld, m->free_pad);
     HIP_TRY(sdfa_launch_gemm(g, s));
     HIP_TRY(sdfa_launch_mesh_scatter(a, s));
     return SDFA_OK;

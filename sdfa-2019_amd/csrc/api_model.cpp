@@ -18,12 +18,24 @@ const std::vector<float> *get(const sdfa_model *m, const std::string &name, size
     return &it->second;
 }
 
+// The host image of the weight blob, and the model's device pointers into it: bind() notes which pointer a slot is for, patch() sets
+// them all once the blob has its device address.
 struct Packer {
     std::vector<float> buf;
+    struct Bind { const float **f; const void **v; size_t o; };
+    std::vector<Bind> binds;
     size_t add(size_t n) {   // 256-byte aligned slots
         size_t o = (buf.size() + 63) / 64 * 64;
         buf.resize(o + n, 0.f);
         return o;
+    }
+    size_t bind(const float *&p, size_t o) { binds.push_back({&p, nullptr, o}); return o; }
+    size_t bind(const void *&p, size_t o) { binds.push_back({nullptr, &p, o}); return o; }
+    void patch(const float *d) const {
+        for (const Bind &b : binds) {
+            if (b.f) *b.f = d + b.o;
+            else *b.v = d + b.o;
+        }
     }
 };
 
@@ -59,6 +71,25 @@ float bf16_bits_to_float(uint16_t b) {
     memcpy(&x, &u, 4);
     return x;
 }
+// x = hi + mid + lo to about 24 bits, each term a bf16: what the split-bf16 kernels multiply (two terms: three products, three terms: six)
+struct Bf16x3 { uint16_t hi, mid, lo; };
+Bf16x3 bf16_split(float x) {
+    Bf16x3 s;
+    s.hi = bf16_rne_bits(x);
+    const float r1 = x - bf16_bits_to_float(s.hi);
+    s.mid = bf16_rne_bits(r1);
+    s.lo = bf16_rne_bits(r1 - bf16_bits_to_float(s.mid));
+    return s;
+}
+// Element e of hidden-state octet o = 4w + 2q + hh of the bf16 recurrences: hidden units 32w+16q+4hh+{0..3} and 32w+16q+8+4hh+{0..3} -- the
+// order in which a lane of the kernels owns its accumulator rows (lstm.hip)
+int rec_octet_k(int o, int e) {
+    const int w = o >> 2, q = (o >> 1) & 1, hh = o & 1;
+    return 32 * w + 16 * q + 4 * hh + (e & 3) + 8 * (e >> 2);
+}
+
+// log2 e and 2 log2 e: the frequency LSTM's gate rows are scaled by them at pack time (sdfa_model_finalize)
+constexpr float LOG2E = 1.4426950408889634f, TWO_LOG2E = 2.8853900817779268f;
 
 // Conv stack weights for conv123_bf16_kernel (conv.hip): three planes (hi | mid | lo) of 1344 octets of 8 bf16 each,
 //   w1 [2 halves][32 co]            k = 8 hh + e: tap df = k / 3, channel c = k % 3 (k >= 9: zero)
@@ -68,11 +99,8 @@ float bf16_bits_to_float(uint16_t b) {
 void pack_conv_bf16(uint16_t *dst, const float *w1, const float *w2, const float *w3) {
     constexpr size_t PLANE = (size_t)1344 * 8;
     auto put = [&](size_t octet, int e, float x) {
-        const uint16_t hi = bf16_rne_bits(x);
-        const float r1 = x - bf16_bits_to_float(hi);
-        const uint16_t mid = bf16_rne_bits(r1);
-        const uint16_t lo = bf16_rne_bits(r1 - bf16_bits_to_float(mid));
-        dst[octet * 8 + e] = hi; dst[PLANE + octet * 8 + e] = mid; dst[2 * PLANE + octet * 8 + e] = lo;
+        const Bf16x3 b = bf16_split(x);
+        dst[octet * 8 + e] = b.hi; dst[PLANE + octet * 8 + e] = b.mid; dst[2 * PLANE + octet * 8 + e] = b.lo;
     };
     for (int hh = 0; hh < 2; ++hh)
         for (int co = 0; co < 32; ++co)
@@ -104,9 +132,9 @@ void pack_pca_bf16(uint16_t *dst, const float *comp_s, const float *comp_r, int6
     for (int64_t tb = 0; tb < ntb; ++tb) {
         uint16_t *blk = dst + (size_t)tb * 2 * PLANE;
         auto put = [&](size_t octet, int e, float x) {
-            const uint16_t hi = bf16_rne_bits(x);
-            blk[octet * 8 + e] = hi;
-            blk[PLANE + octet * 8 + e] = bf16_rne_bits(x - bf16_bits_to_float(hi));
+            const Bf16x3 b = bf16_split(x);      // two planes: the second term is this kernel's "lo"
+            blk[octet * 8 + e] = b.hi;
+            blk[PLANE + octet * 8 + e] = b.mid;
         };
         for (int r = 0; r < 12; ++r)
             for (int c = 0; c < 192; ++c)
@@ -127,45 +155,29 @@ void pack_pca_bf16(uint16_t *dst, const float *comp_s, const float *comp_r, int6
 
 // Frequency-LSTM weights for freq_lstm_bf16_kernel / freq_lstm_bf16x6_kernel: per direction [plane hi | mid | lo][24 octets][512 gate rows][8] bf16.
 // cat = [W_ih | W_hh] rows in torch order, perm = packed gate row -> torch row.  Octets 0..7 are the 64 input features
-// in order; octet 8 + o' (o' = 4w + 2q + hh) holds hidden units 32w+16q+4hh+{0..3} and 32w+16q+8+4hh+{0..3} -- the order
-// in which a lane of the kernel owns its accumulator rows (lstm.hip).
+// in order; octet 8 + o' holds the hidden units of rec_octet_k(o', .).
 void pack_freq_lstm_bf16(uint16_t *dst, const float *cat, const int *perm) {
     for (int O = 0; O < 24; ++O)
         for (int p = 0; p < 512; ++p)
             for (int e = 0; e < 8; ++e) {
-                int k;
-                if (O < 8) k = 8 * O + e;
-                else {
-                    const int o = O - 8, w = o >> 2, q = (o >> 1) & 1, hh = o & 1;
-                    k = 64 + 32 * w + 16 * q + 4 * hh + (e & 3) + 8 * (e >> 2);
-                }
-                const float x = cat[(size_t)perm[p] * 192 + k];
-                const uint16_t hi = bf16_rne_bits(x);
-                const float r1 = x - bf16_bits_to_float(hi);
-                const uint16_t mid = bf16_rne_bits(r1);
-                const uint16_t lo = bf16_rne_bits(r1 - bf16_bits_to_float(mid));
-                dst[((size_t)O * 512 + p) * 8 + e] = hi;
-                dst[((size_t)(24 + O) * 512 + p) * 8 + e] = mid;      // the "lo" plane of the three-product split
-                dst[((size_t)(48 + O) * 512 + p) * 8 + e] = lo;       // third term: six-product split only
+                const int k = O < 8 ? 8 * O + e : 64 + rec_octet_k(O - 8, e);
+                const Bf16x3 b = bf16_split(cat[(size_t)perm[p] * 192 + k]);
+                dst[((size_t)O * 512 + p) * 8 + e] = b.hi;
+                dst[((size_t)(24 + O) * 512 + p) * 8 + e] = b.mid;      // the "lo" plane of the three-product split
+                dst[((size_t)(48 + O) * 512 + p) * 8 + e] = b.lo;       // third term: six-product split only
             }
 }
 
 // Recurrent weights of one BiLSTM direction for time_lstm_bf16_kernel: [plane hi | mid | lo][32 octets][1024 gate rows][8] bf16,
-// the K axis (256 hidden units) in the accumulator-row order of the kernel (same octet rule as above).
+// the K axis (256 hidden units) in the accumulator-row order of the kernel (rec_octet_k).
 void pack_rec_bf16(uint16_t *dst, const float *whh, const int *perm) {
     for (int o = 0; o < 32; ++o)
         for (int p = 0; p < 1024; ++p)
             for (int e = 0; e < 8; ++e) {
-                const int w = o >> 2, q = (o >> 1) & 1, hh = o & 1;
-                const int k = 32 * w + 16 * q + 4 * hh + (e & 3) + 8 * (e >> 2);
-                const float x = whh[(size_t)perm[p] * 256 + k];
-                const uint16_t hi = bf16_rne_bits(x);
-                const float r1 = x - bf16_bits_to_float(hi);
-                const uint16_t mid = bf16_rne_bits(r1);
-                const uint16_t lo = bf16_rne_bits(r1 - bf16_bits_to_float(mid));
-                dst[((size_t)o * 1024 + p) * 8 + e] = hi;
-                dst[((size_t)(32 + o) * 1024 + p) * 8 + e] = mid;
-                dst[((size_t)(64 + o) * 1024 + p) * 8 + e] = lo;
+                const Bf16x3 b = bf16_split(whh[(size_t)perm[p] * 256 + rec_octet_k(o, e)]);
+                dst[((size_t)o * 1024 + p) * 8 + e] = b.hi;
+                dst[((size_t)(32 + o) * 1024 + p) * 8 + e] = b.mid;
+                dst[((size_t)(64 + o) * 1024 + p) * 8 + e] = b.lo;
             }
 }
 
@@ -183,21 +195,19 @@ void pack_rec_16x16x4(float *dst, const float *whh, const int *perm) {
                 }
 }
 
-int pack_fc(sdfa_model *m, Packer &pk, const std::string &key, int P, int Kin, bool cond, int act, size_t off[3],
-            sdfa_model::Fc &fc) {
+int pack_fc(sdfa_model *m, Packer &pk, const std::string &key, int P, int Kin, bool cond, int act, sdfa_model::Fc &fc) {
     const int Ktot = cond ? Kin + 8 : Kin;
     auto *w = get(m, key + ".weight", (size_t)P * Ktot);
     auto *b = get(m, key + ".bias", P);
     if (!w || !b) return SDFA_ESTATE;
     fc.K = Kin; fc.P = P; fc.Ppad = (int)round_up(P, 128); fc.Pstore = (int)round_up(P, 32); fc.act = act;
-    off[0] = pack_k4(pk, w->data(), P, Kin, Ktot, 0, Kin, fc.Ppad);
-    off[1] = pk.add(fc.Ppad);
-    memcpy(&pk.buf[off[1]], b->data(), P * 4);
-    off[2] = (size_t)-1;
+    pk.bind(fc.w, pack_k4(pk, w->data(), P, Kin, Ktot, 0, Kin, fc.Ppad));
+    memcpy(&pk.buf[pk.bind(fc.b, pk.add(fc.Ppad))], b->data(), P * 4);
+    fc.cw = nullptr;
     if (cond) {
-        off[2] = pk.add((size_t)fc.Ppad * 8);
+        const size_t o = pk.bind(fc.cw, pk.add((size_t)fc.Ppad * 8));
         for (int p = 0; p < P; ++p)
-            for (int s = 0; s < 8; ++s) pk.buf[off[2] + ((size_t)(p / 4) * 8 + s) * 4 + (p % 4)] = (*w)[(size_t)p * Ktot + Kin + s];
+            for (int s = 0; s < 8; ++s) pk.buf[o + ((size_t)(p / 4) * 8 + s) * 4 + (p % 4)] = (*w)[(size_t)p * Ktot + Kin + s];
     }
     return SDFA_OK;
 }
@@ -240,7 +250,7 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
     Packer pk;
     const std::string enc = "_audio_encoder._layers.";
     // ---- conv stack: fold eval BatchNorm (eps 1e-3) into scale/shift applied AFTER LeakyReLU (extend.py:94-101)
-    size_t o_conv[3][4];
+    const float **conv_p[3][4] = {{&m->w1, &m->b1, &m->s1, &m->t1}, {&m->w2, &m->b2, &m->s2, &m->t2}, {&m->w3, &m->b3, &m->s3, &m->t3}};   // weights, bias, BN scale, BN shift
     const std::vector<float> *conv_w[3] = {nullptr, nullptr, nullptr};
     const int cshape[3][3] = {{32, 3, 3}, {64, 32, 3}, {64, 64, 1}};   // co, ci, kf
     const int cidx[3] = {1, 3, 5};
@@ -254,14 +264,14 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
         if (!w || !b || !g || !be || !mu || !var) return SDFA_ESTATE;
         conv_w[l] = w;
         if (l == 0) {   // A operand [5 k-steps][2 halves][32 co], k = df*3 + c, k = 9 -> 0
-            o_conv[0][0] = pk.add(5 * 2 * 32);
+            const size_t o_w1 = pk.bind(*conv_p[0][0], pk.add(5 * 2 * 32));
             for (int s = 0; s < 5; ++s)
                 for (int hh = 0; hh < 2; ++hh)
                     for (int o = 0; o < 32; ++o) {
                         const int kk = 2 * s + hh;
                         float v = 0.f;
                         if (kk < 9) { const int df = kk / 3, c = kk % 3; v = (*w)[((size_t)o * 3 + c) * 3 + df]; }
-                        pk.buf[o_conv[0][0] + (s * 2 + hh) * 32 + o] = v;
+                        pk.buf[o_w1 + (s * 2 + hh) * 32 + o] = v;
                     }
         } else {        // K4 [K/4][64][4], k = df*ci + c
             const int K = ci * kf;
@@ -269,27 +279,28 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
             for (int o = 0; o < co; ++o)
                 for (int c = 0; c < ci; ++c)
                     for (int df = 0; df < kf; ++df) flat[(size_t)o * K + df * ci + c] = (*w)[((size_t)o * ci + c) * kf + df];
-            o_conv[l][0] = pack_k4(pk, flat.data(), co, K, K, 0, K, co);
+            pk.bind(*conv_p[l][0], pack_k4(pk, flat.data(), co, K, K, 0, K, co));
         }
-        o_conv[l][1] = pk.add(co); o_conv[l][2] = pk.add(co); o_conv[l][3] = pk.add(co);
+        size_t o_bst[3];
+        for (int i = 0; i < 3; ++i) o_bst[i] = pk.bind(*conv_p[l][1 + i], pk.add(co));
         for (int o = 0; o < co; ++o) {
             const double sc = (double)(*g)[o] / std::sqrt((double)(*var)[o] + 1e-3);
-            pk.buf[o_conv[l][1] + o] = (*b)[o];
-            pk.buf[o_conv[l][2] + o] = (float)sc;
-            pk.buf[o_conv[l][3] + o] = (float)((double)(*be)[o] - (double)(*mu)[o] * sc);
+            pk.buf[o_bst[0] + o] = (*b)[o];
+            pk.buf[o_bst[1] + o] = (float)sc;
+            pk.buf[o_bst[2] + o] = (float)((double)(*be)[o] - (double)(*mu)[o] * sc);
         }
     }
-    const size_t o_cvwb = pk.add((size_t)3 * 1344 * 8 / 2);      // three bf16 planes of 1344 octets, two bf16 per float slot
+    const size_t o_cvwb = pk.bind(m->cv_wb, pk.add((size_t)3 * 1344 * 8 / 2));      // three bf16 planes of 1344 octets, two bf16 per float slot
     pack_conv_bf16(reinterpret_cast<uint16_t *>(&pk.buf[o_cvwb]), conv_w[0]->data(), conv_w[1]->data(), conv_w[2]->data());
     // ---- frequency LSTM: [W_ih | W_hh] concatenated along K, gate rows packed per wave; bias = b_ih + b_hh
-    size_t o_flw = pk.add(0), o_flb, o_flwb;
     {
-        o_flwb = pk.add((size_t)2 * 3 * 24 * 512 * 8 / 2);   // two directions x three bf16 planes, two bf16 per float slot
+        const size_t o_flwb = pk.bind(m->fl_wb, pk.add((size_t)2 * 3 * 24 * 512 * 8 / 2));   // two directions x three bf16 planes, two bf16 per float slot
         const auto perm = gate_perm(128);
         const char *suf[2] = {"", "_reverse"};
         std::vector<float> cat((size_t)512 * 192);
         size_t first = 0;
         std::vector<float> bias(1024);
+        auto gate_scale = [](int torch_row) { return torch_row / 128 == 2 ? TWO_LOG2E : LOG2E; };      // gate order i, f, g, o
         for (int d = 0; d < 2; ++d) {
             const std::string k = enc + "6._lstm.";
             auto *wih = get(m, k + "weight_ih_l0" + suf[d], 512 * 64), *whh = get(m, k + "weight_hh_l0" + suf[d], 512 * 128);
@@ -301,35 +312,31 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
             // per element pair less (round 4; lstm.hip: lstm_cell_quad<true>).  A weight picks up one more fp32 rounding; the stage
             // stays inside its 1e-4 tap tolerance (tests/test_gpu_parity.py) and all launch forms share the packed weights.
             for (int r = 0; r < 512; ++r) {
-                const float k = (r / 128 == 2) ? 2.8853900817779268f : 1.4426950408889634f;
+                const float k = gate_scale(r);
                 for (int j = 0; j < 64; ++j) cat[(size_t)r * 192 + j] = (*wih)[(size_t)r * 64 + j] * k;
                 for (int j = 0; j < 128; ++j) cat[(size_t)r * 192 + 64 + j] = (*whh)[(size_t)r * 128 + j] * k;
             }
             size_t o = pack_k4(pk, cat.data(), 512, 192, 192, 0, 192, 512, perm.data());
             pack_freq_lstm_bf16(reinterpret_cast<uint16_t *>(&pk.buf[o_flwb]) + (size_t)d * 3 * 24 * 512 * 8, cat.data(), perm.data());
-            if (d == 0) first = o;
+            if (d == 0) first = pk.bind(m->fl_w, o);
             else if (o != first + (size_t)48 * 512 * 4) return sdfa_fail(SDFA_ESTATE, "internal: freq-lstm weights not contiguous");
             for (int p = 0; p < 512; ++p)
-                bias[d * 512 + p] = ((*bih)[perm[p]] + (*bhh)[perm[p]]) * ((perm[p] / 128 == 2) ? 2.8853900817779268f : 1.4426950408889634f);
+                bias[d * 512 + p] = ((*bih)[perm[p]] + (*bhh)[perm[p]]) * gate_scale(perm[p]);
         }
-        o_flw = first;
-        o_flb = pk.add(1024);
-        memcpy(&pk.buf[o_flb], bias.data(), 1024 * 4);
+        memcpy(&pk.buf[pk.bind(m->fl_b, pk.add(1024))], bias.data(), 1024 * 4);
     }
-    size_t o_fpw, o_fpb;
     {
         auto *w = get(m, enc + "6._proj.weight", (size_t)256 * 8192), *b = get(m, enc + "6._proj.bias", 256);
         if (!w || !b) return SDFA_ESTATE;
-        o_fpw = pack_k4(pk, w->data(), 256, 8192, 8192, 0, 8192, 256);
-        o_fpb = pk.add(256);
-        memcpy(&pk.buf[o_fpb], b->data(), 256 * 4);
+        pk.bind(m->fp_w, pack_k4(pk, w->data(), 256, 8192, 8192, 0, 8192, 256));
+        memcpy(&pk.buf[pk.bind(m->fp_b, pk.add(256))], b->data(), 256 * 4);
     }
     // ---- time BiLSTM (bias=False): input projections as one 2048-row GEMM per layer, recurrent weights K4
-    size_t o_gx[2], o_tl[2], o_tlb[2], o_tl16[2];
     {
+        size_t o_tlb[2], o_tl16[2];
         const auto perm = gate_perm(256);
-        for (int l = 0; l < 2; ++l) o_tlb[l] = pk.add((size_t)2 * 3 * 32 * 1024 * 8 / 2);   // two directions x three bf16 planes, two bf16 per float slot
-        for (int l = 0; l < 2; ++l) o_tl16[l] = pk.add((size_t)2 * 16 * 4 * 1024 * 4);      // two directions, 16x16x4 operand order
+        for (int l = 0; l < 2; ++l) o_tlb[l] = pk.bind(m->tl_wb[l], pk.add((size_t)2 * 3 * 32 * 1024 * 8 / 2));   // two directions x three bf16 planes, two bf16 per float slot
+        for (int l = 0; l < 2; ++l) o_tl16[l] = pk.bind(m->tl_w16[l], pk.add((size_t)2 * 16 * 4 * 1024 * 4));      // two directions, 16x16x4 operand order
         const char *suf[2] = {"", "_reverse"};
         for (int l = 0; l < 2; ++l) {
             const int Kin = l == 0 ? 256 : 512;
@@ -343,43 +350,43 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
                 size_t o = pack_k4(pk, whh->data(), 1024, 256, 256, 0, 256, 1024, perm.data());
                 pack_rec_bf16(reinterpret_cast<uint16_t *>(&pk.buf[o_tlb[l]]) + (size_t)d * 3 * 32 * 1024 * 8, whh->data(), perm.data());
                 pack_rec_16x16x4(&pk.buf[o_tl16[l]] + (size_t)d * 16 * 4 * 1024 * 4, whh->data(), perm.data());
-                if (d == 0) first = o;
+                if (d == 0) first = pk.bind(m->tl_w[l], o);
                 else if (o != first + (size_t)64 * 1024 * 4) return sdfa_fail(SDFA_ESTATE, "internal: time-lstm weights not contiguous");
             }
-            o_tl[l] = first;
-            o_gx[l] = pack_k4(pk, both.data(), 2048, Kin, Kin, 0, Kin, 2048);
+            pk.bind(m->gx_w[l], pack_k4(pk, both.data(), 2048, Kin, Kin, 0, Kin, 2048));
         }
     }
     // ---- attention
-    size_t o_kp, o_qc, o_qp, o_v, o_b;
     {
         const std::string k = enc + "10.";
         auto *cq = get(m, k + "_conv_query.weight", (size_t)512 * 512 * 3), *wk = get(m, k + "proj_key.weight", 128 * 512);
         auto *wq = get(m, k + "proj_qry.weight", 128 * 512), *v = get(m, k + "v.weight", 128), *b = get(m, k + "b", 128);
         if (!cq || !wk || !wq || !v || !b) return SDFA_ESTATE;
-        o_kp = pack_k4(pk, wk->data(), 128, 512, 512, 0, 512, 128);
-        o_qp = pack_k4(pk, wq->data(), 128, 512, 512, 0, 512, 128);
+        pk.bind(m->kp_w, pack_k4(pk, wk->data(), 128, 512, 512, 0, 512, 128));
+        pk.bind(m->qp_w, pack_k4(pk, wq->data(), 128, 512, 512, 0, 512, 128));
         std::vector<float> flat((size_t)512 * 1536);   // k = tap*512 + c
         for (int o = 0; o < 512; ++o)
             for (int c = 0; c < 512; ++c)
                 for (int t = 0; t < 3; ++t) flat[(size_t)o * 1536 + t * 512 + c] = (*cq)[((size_t)o * 512 + c) * 3 + t];
-        o_qc = pack_k4(pk, flat.data(), 512, 1536, 1536, 0, 1536, 512);
-        o_v = pk.add(128); memcpy(&pk.buf[o_v], v->data(), 512);
-        o_b = pk.add(128); memcpy(&pk.buf[o_b], b->data(), 512);
+        pk.bind(m->qc_w, pack_k4(pk, flat.data(), 512, 1536, 1536, 0, 1536, 512));
+        memcpy(&pk.buf[pk.bind(m->at_v, pk.add(128))], v->data(), 512);
+        memcpy(&pk.buf[pk.bind(m->at_b, pk.add(128))], b->data(), 512);
     }
     // ---- output module
     const std::string om = "_output_module.";
-    size_t o_fc[7][3];
-    size_t o_pq[2] = {0, 0}, o_pb[2] = {0, 0}, o_pqb = 0;
-    bool have_pqb = false;
+    // PCA basis b: compT [cols][kreal] as the K4 operand [pca_K / 4][pca_ld][4] (zero padded), means [pca_ld]
+    auto pack_basis = [&](int b, const std::vector<float> &compT, int kreal, const std::vector<float> &means) {
+        pk.bind(m->pca_q[b], pack_k4(pk, compT.data(), (int)m->pca_cols[b], kreal, kreal, 0, m->pca_K[b], (int)m->pca_ld[b]));
+        memcpy(&pk.buf[pk.bind(m->pca_bias[b], pk.add(m->pca_ld[b]))], means.data(), m->pca_cols[b] * 4);
+    };
     if (m->head == SDFA_HEAD_DGRAD) {
-        if (pack_fc(m, pk, om + "_layers.0", 512, 512, true, ACT_LRELU, o_fc[0], m->trunk)) return SDFA_ESTATE;
+        if (pack_fc(m, pk, om + "_layers.0", 512, 512, true, ACT_LRELU, m->trunk)) return SDFA_ESTATE;
         const char *brn[2] = {"_scale_layers.", "_rotat_layers."};
         const int nco[2] = {SDFA_COEF_SCALE, SDFA_COEF_ROTAT};
         for (int b = 0; b < 2; ++b) {
-            if (pack_fc(m, pk, om + brn[b] + "0", 512, 512, true, ACT_LRELU, o_fc[1 + 3 * b], m->br[b][0])) return SDFA_ESTATE;
-            if (pack_fc(m, pk, om + brn[b] + "1", 256, 512, false, ACT_TANH, o_fc[2 + 3 * b], m->br[b][1])) return SDFA_ESTATE;
-            if (pack_fc(m, pk, om + brn[b] + "2", nco[b], 256, false, ACT_NONE, o_fc[3 + 3 * b], m->br[b][2])) return SDFA_ESTATE;
+            if (pack_fc(m, pk, om + brn[b] + "0", 512, 512, true, ACT_LRELU, m->br[b][0])) return SDFA_ESTATE;
+            if (pack_fc(m, pk, om + brn[b] + "1", 256, 512, false, ACT_TANH, m->br[b][1])) return SDFA_ESTATE;
+            if (pack_fc(m, pk, om + brn[b] + "2", nco[b], 256, false, ACT_NONE, m->br[b][2])) return SDFA_ESTATE;
         }
         auto *cs = get(m, om + "_scale_pca.compT", (size_t)59856 * 85), *ms = get(m, om + "_scale_pca.means", 59856);
         auto *cr = get(m, om + "_rotat_pca.compT", (size_t)29928 * 180), *mr = get(m, om + "_rotat_pca.means", 29928);
@@ -392,61 +399,29 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
         for (int b = 0; b < 2; ++b) {
             m->pca_K[b] = b ? 192 : 96; m->pca_k0[b] = b ? 96 : 0; m->pca_group[b] = b ? 3 : 6; m->pca_off[b] = b ? 6 : 0;
             m->pca_cols[b] = b ? 29928 : 59856; m->pca_ld[b] = round_up(m->pca_cols[b], 128);
-            o_pq[b] = pk.add((size_t)m->pca_K[b] * m->pca_ld[b]);
-            o_pb[b] = pk.add(m->pca_ld[b]);
-            for (int64_t o = 0; o < m->pca_cols[b]; ++o) {
-                const float *row = &(*comp[b])[(size_t)o * kreal[b]];
-                for (int k = 0; k < kreal[b]; ++k) pk.buf[o_pq[b] + ((size_t)(k / 4) * m->pca_ld[b] + o) * 4 + (k % 4)] = row[k];
-                pk.buf[o_pb[b] + o] = (*mean[b])[o];
-            }
+            pack_basis(b, *comp[b], kreal[b], *mean[b]);
         }
         {   // the same bases as bf16 octets for the split-bf16 form of the fused kernel
             const int64_t ntb = (m->pca_cols[1] + 95) / 96;
-            o_pqb = pk.add((size_t)ntb * 2 * (12 * 192 + 24 * 96) * 8 / 2);      // two bf16 per float slot
+            const size_t o_pqb = pk.bind(m->pca_qb, pk.add((size_t)ntb * 2 * (12 * 192 + 24 * 96) * 8 / 2));      // two bf16 per float slot
             pack_pca_bf16(reinterpret_cast<uint16_t *>(&pk.buf[o_pqb]), cs->data(), cr->data(), m->pca_cols[0], m->pca_cols[1], ntb);
-            have_pqb = true;
         }
     } else {
-        if (pack_fc(m, pk, om + "_layers.0", 512, 512, true, ACT_LRELU, o_fc[0], m->off[0])) return SDFA_ESTATE;
-        if (pack_fc(m, pk, om + "_layers.1", 256, 512, false, ACT_TANH, o_fc[1], m->off[1])) return SDFA_ESTATE;
-        if (pack_fc(m, pk, om + "_layers.2", SDFA_COEF_OFFSETS, 256, false, ACT_NONE, o_fc[2], m->off[2])) return SDFA_ESTATE;
+        if (pack_fc(m, pk, om + "_layers.0", 512, 512, true, ACT_LRELU, m->off[0])) return SDFA_ESTATE;
+        if (pack_fc(m, pk, om + "_layers.1", 256, 512, false, ACT_TANH, m->off[1])) return SDFA_ESTATE;
+        if (pack_fc(m, pk, om + "_layers.2", SDFA_COEF_OFFSETS, 256, false, ACT_NONE, m->off[2])) return SDFA_ESTATE;
         auto *cp = get(m, om + "_pca.compT", (size_t)SDFA_OFFSETS_DIM * 59), *mp = get(m, om + "_pca.means", SDFA_OFFSETS_DIM);
         if (!cp || !mp) return SDFA_ESTATE;
         m->pca_n = 1;
         m->pca_K[0] = 64; m->pca_k0[0] = 0; m->pca_group[0] = 0; m->pca_off[0] = 0;
         m->pca_cols[0] = SDFA_OFFSETS_DIM; m->pca_ld[0] = round_up(SDFA_OFFSETS_DIM, 128);
-        o_pq[0] = pk.add((size_t)m->pca_K[0] * m->pca_ld[0]);
-        o_pb[0] = pk.add(m->pca_ld[0]);
-        for (int64_t o = 0; o < SDFA_OFFSETS_DIM; ++o) {
-            for (int k = 0; k < 59; ++k) pk.buf[o_pq[0] + ((size_t)(k / 4) * m->pca_ld[0] + o) * 4 + (k % 4)] = (*cp)[(size_t)o * 59 + k];
-            pk.buf[o_pb[0] + o] = (*mp)[o];
-        }
+        pack_basis(0, *cp, 59, *mp);
     }
     // ---- upload
     HIP_TRY(hipMalloc(&m->blob, pk.buf.size() * 4));
     HIP_TRY(hipMemcpyAsync(m->blob, pk.buf.data(), pk.buf.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));   // host staging buffer dies with this call
-    const float *d = (const float *)m->blob;
-    m->w1 = d + o_conv[0][0]; m->b1 = d + o_conv[0][1]; m->s1 = d + o_conv[0][2]; m->t1 = d + o_conv[0][3];
-    m->w2 = d + o_conv[1][0]; m->b2 = d + o_conv[1][1]; m->s2 = d + o_conv[1][2]; m->t2 = d + o_conv[1][3];
-    m->w3 = d + o_conv[2][0]; m->b3 = d + o_conv[2][1]; m->s3 = d + o_conv[2][2]; m->t3 = d + o_conv[2][3];
-    m->fl_wb = d + o_flwb;
-    m->cv_wb = d + o_cvwb;
-    m->fl_w = d + o_flw; m->fl_b = d + o_flb; m->fp_w = d + o_fpw; m->fp_b = d + o_fpb;
-    for (int l = 0; l < 2; ++l) { m->gx_w[l] = d + o_gx[l]; m->tl_w[l] = d + o_tl[l]; m->tl_wb[l] = d + o_tlb[l]; m->tl_w16[l] = d + o_tl16[l]; }
-    m->kp_w = d + o_kp; m->qc_w = d + o_qc; m->qp_w = d + o_qp; m->at_v = d + o_v; m->at_b = d + o_b;
-    auto bind = [&](sdfa_model::Fc &fc, size_t o[3]) {
-        fc.w = d + o[0]; fc.b = d + o[1]; fc.cw = o[2] == (size_t)-1 ? nullptr : d + o[2];
-    };
-    if (m->head == SDFA_HEAD_DGRAD) {
-        bind(m->trunk, o_fc[0]);
-        for (int b = 0; b < 2; ++b)
-            for (int i = 0; i < 3; ++i) bind(m->br[b][i], o_fc[1 + 3 * b + i]);
-    } else {
-        for (int i = 0; i < 3; ++i) bind(m->off[i], o_fc[i]);
-    }
-    for (int b = 0; b < m->pca_n; ++b) { m->pca_q[b] = d + o_pq[b]; m->pca_bias[b] = d + o_pb[b]; }
-    if (have_pqb) m->pca_qb = d + o_pqb;
+    pk.patch((const float *)m->blob);
     m->host.clear();
     m->finalized = true;
     return SDFA_OK;

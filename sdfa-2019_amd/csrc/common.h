@@ -93,9 +93,9 @@ __device__ __forceinline__ void st4(float *p, const float4 &v) { *reinterpret_ca
 
 // CUs of the CURRENT device, looked up per launch (a process may drive differently sized or CU-masked devices; a function-local
 // static would freeze the first device's count -- ADVICE r3).  The attribute query is a table lookup in the runtime; the small
-// per-device cache only saves the call.
+// per-device cache only saves the call.  (Always inlined: the library exports no function of its own but the C ABI.)
 #include <atomic>
-inline int sdfa_cu_count() {
+__attribute__((always_inline)) inline int sdfa_cu_count() {
     static std::atomic<int> cache[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 256;

@@ -38,6 +38,16 @@ struct GemmArgs {
     int reserve_cus;          // persistent kernel (gemm_fat_kernel): launch (CUs - reserve_cus) workgroups
 };
 hipError_t sdfa_launch_gemm(const GemmArgs &a, hipStream_t s);
+// The plain product: K4 P [K/4][rows] x K4 Q [K/4][ldq] -> K4 D [rows][cols], one segment, every row and column stored, no bias, no
+// activation, fp32.  Call sites set what differs from that (terms, reserve_cus, segments, a bias, ...) on the result.
+inline GemmArgs sdfa_gemm_k4(const float *P, int64_t rows, const float *Q, int64_t ldq, float *D, int64_t cols, int K) {
+    GemmArgs g{};
+    g.P = P; g.Q = Q; g.D = D;
+    g.ldp = rows; g.Ppad = rows; g.Pstore = rows;
+    g.ldq = ldq; g.ldd = cols; g.Qpad = cols; g.Qreal = cols;
+    g.K = K; g.seg_k = K; g.act = ACT_NONE; g.out_mode = OUT_K4;
+    return g;
+}
 
 // ---- PCA expansion of the dgrad head, both bases fused (pca.hip) ---------------------------------
 struct PcaArgs {
@@ -210,6 +220,17 @@ struct ShareArgs {
     uint64_t *hash;              // [N * 64] scratch: 64-bit hash of each column's bit pattern, frame-major
     uint64_t *linked;            // [N] scratch: bit t = column t of frame n has been compared in full with column t + shift[n] of frame prev[n], and is equal
 };
+// All of a map's tables live in one int32 region: [counts: 16 words | prev | shift | owner | flag | uid | col_src | col_to_u | tile_sum].
+// (counts takes the first four of its 16 words; the front end keeps its stream kernel's status in word 8.)
+// sdfa_share_table_words is what that takes (tile_sum: one word per 1024 columns, share.hip: launch_share_numbering, and one to spare); a workspace
+// layout reserves at least that much, sdfa_share_carve (N / Nc / Mc set before) points the arguments into it.
+inline int64_t sdfa_share_table_words(int64_t Nc) { return 16 + 2 * Nc + 5 * (64 * Nc) + (64 * Nc) / 1024 + 1; }
+inline void sdfa_share_carve(ShareArgs &a, int32_t *base) {
+    a.counts = reinterpret_cast<int64_t *>(base);
+    a.prev = base + 16; a.shift = a.prev + a.Nc;
+    a.owner = a.shift + a.Nc; a.flag = a.owner + a.Mc; a.uid = a.flag + a.Mc;
+    a.col_src = a.uid + a.Mc; a.col_to_u = a.col_src + a.Mc; a.tile_sum = a.col_to_u + a.Mc;
+}
 hipError_t sdfa_launch_share_map(const ShareArgs &a, hipStream_t s);
 hipError_t sdfa_launch_share_map_content(const ShareArgs &a, hipStream_t s);   // the same map, built from the contents of audio_feat (t_lo / t_hi / frame_clip / frame_start / hop unused)
 hipError_t sdfa_launch_share_prev(const ShareArgs &a, hipStream_t s);     // prev / shift only (the spectral-stream front end reads the chains from them)

@@ -442,8 +442,7 @@ hipError_t sdfa_launch_pca_dgrad_res(const PcaArgs &a, int *queue, hipStream_t s
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(queue, 0, sizeof(int), s);
     if (e != hipSuccess) return e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    int cus = sdfa_cu_count();
     // work unit = one triangle block x `fbu` frame blocks: the slab is loaded once per unit, so large units are cheaper, but the
     // queue should still hold several units per CU for balance
     const int64_t nfb = a.Nc / 128;

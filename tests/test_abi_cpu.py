@@ -122,3 +122,44 @@ def test_legacy_checkpoint_renames():
     st = weights.ckpt_backward_compatible_preprocess(ck)["state"]
     assert set(st) == {"_model._audio_encoder._layers.1.weight_v", "_model._output_module._scale_pca.compT",
                        "_model._audio_encoder._layers.10.b", "_model._audio_encoder._layers.1._ext_post_bn.weight"}
+
+
+# (frames, sdfa_workspace_bytes keep-intermediates off, on, sdfa_frontend_workspace_bytes), as the library returned them before the
+# layouts' share-map tables and scratch offsets were given one definition each: the sizes are part of what callers allocate by
+WORKSPACE_BYTES = [
+    (1, 404727808, 526362624, 4359424),
+    (128, 404727808, 526362624, 4359424),
+    (129, 809446400, 1052716032, 8718592),
+    (700, 2428320768, 3158129664, 26155520),
+    (2048, 6475506944, 8421664000, 69747456),
+    (8192, 25902000896, 33686629120, 278989056),
+    (20352, 64350270208, 83690205952, 693113088),
+]
+
+
+def test_workspace_sizes_are_pinned_and_cover_the_share_tables():
+    """Host code only: sdfa_workspace_bytes reads the model's keep flag and nothing else, so an unfinalised model will do."""
+    lib = _lib.lib
+    m = lib.sdfa_model_create(_lib.HEAD_DGRAD)
+    assert m
+    try:
+        for n, keep_off, keep_on, frontend in WORKSPACE_BYTES:
+            assert lib.sdfa_debug_keep_intermediates(m, 0) == _lib.OK
+            assert lib.sdfa_workspace_bytes(m, n) == keep_off, n
+            assert lib.sdfa_debug_keep_intermediates(m, 1) == _lib.OK
+            assert lib.sdfa_workspace_bytes(m, n) == keep_on, n
+            assert lib.sdfa_frontend_workspace_bytes(n) == frontend, n
+            # What the share-map tables need (kernels.h: sdfa_share_table_words, written out again here): 16 counter words, prev / shift
+            # [Nc], owner / flag / uid / col_src / col_to_u [Mc], one scan word per 1024 columns and one to spare.
+            Nc = (n + 127) // 128 * 128
+            Mc = 64 * Nc
+            need = 16 + 2 * Nc + 5 * Mc + Mc // 1024 + 1
+            # front end: the tables, then the mel table of 128 floats per column
+            assert frontend % 4 == 0 and frontend // 4 - 128 * Mc >= need, n
+            # encoder, nothing kept: every other region is a multiple of 64 words -- status 64, pool1 / conv3 2048 Mc each, the
+            # frequency LSTM's hidden states 8192 Mc, query conv / query / context 512 + 128 + 512 Nc, regressor 2560 Nc, control 2048
+            assert keep_off % 4 == 0 and keep_off // 4 - (64 + 12288 * Mc + 3712 * Nc + 2048) >= need, n
+            # kept: 2048 + 2048 + 8192 + 256 + 2048 + 512 + 512 + 128 Mc, and the distinct-column projection's own 256 Mc
+            assert keep_on % 4 == 0 and keep_on // 4 - (64 + 16000 * Mc + 3712 * Nc + 2048) >= need, n
+    finally:
+        lib.sdfa_model_destroy(m)
