@@ -311,6 +311,9 @@ int sdfa_ensemble_mean(const float *d_a, const float *d_b, int64_t n, float *d_o
  *   "encoder_dedup_off" 1 = sdfa_encoder_forward (no frame table) evaluates every column of every frame, as it did before it learnt to find the
  *                      identical columns of audio_feat itself (hash, then a full bit-pattern compare of every proposed pair, on the device, on
  *                      every call); the every-column path is the reference the sharing tests compare against.  Same bits
+ *   "freq_proj_tail"   the shared-column frequency projection (fp32, chunks of 2,048 frames and more): the column tiles behind the last whole
+ *                      round of the persistent GEMM's grid go to a fine-tile kernel (gemm_tail.hip) instead of costing a round of their own.
+ *                      0 = where the device-side rule says it pays (default), 1 = never (one launch, as before), 2 = always.  Same bits
  *   "conv_fp32"        1 = the body precision modes (bf16, bf16x3, bf16x6) keep the conv stack on the fp32 kernel instead of
  *                      conv123_bf16_kernel (NOT bit-identical: that stack's operand rounding)
  *   "pca_fp32"         1 = SDFA_PREC_BF16X3 keeps the dgrad PCA expansion on the fp32 kernel (NOT bit-identical: the expansion's operand rounding)

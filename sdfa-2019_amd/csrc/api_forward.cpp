@@ -1,5 +1,6 @@
 // C ABI of libsdfa_hip.so (include/sdfa_hip.h): the forward calls -- workspace layout and status, profiling, precision modes,
 // autotune, encoder / regressor / PCA expansion, debug taps.
+#include "common.h"
 #include "host.h"
 #include "kernels.h"
 #include "model.h"
@@ -7,7 +8,8 @@
 #include <algorithm>
 
 // A/B options this file reads (api_core.cpp)
-extern thread_local int g_sdfa_freq_lstm_shape, g_sdfa_pca_lds, g_sdfa_pca_fp32, g_sdfa_conv_fp32, g_sdfa_share_gx0_off, g_sdfa_attn_unfused, g_sdfa_encoder_dedup_off;
+extern thread_local int g_sdfa_gemm_variant, g_sdfa_freq_lstm_shape, g_sdfa_pca_lds, g_sdfa_pca_fp32, g_sdfa_conv_fp32, g_sdfa_share_gx0_off, g_sdfa_attn_unfused, g_sdfa_encoder_dedup_off,
+    g_sdfa_freq_proj_tail;
 
 // ================================================================================================
 // workspace layout (floats), per chunk of Nc frames, Mc = 64*Nc columns
@@ -189,10 +191,19 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         const bool share = table || (!m->keep && !g_sdfa_encoder_dedup_off);
         const int64_t *d_ulimit = nullptr;     // device scalar: number of distinct columns, padded to 256
         int32_t *col_to_u = nullptr;
+        bool split_tail = false;               // the frequency projection as whole rounds of gemm_fat_kernel + sdfa_launch_gemm_tail
+        int64_t fat_grid = 0;
+        const int64_t *d_qfull = nullptr;
         if (share) {
             ShareArgs sa{};
             sa.N = N; sa.Nc = Nc; sa.Mc = Mc;
             sdfa_share_carve(sa, reinterpret_cast<int32_t *>(ws + w.SH));
+            // the fat kernel is what multiplies the projection (gemm.hip: launch_any): its last partial round goes to the tail kernel
+            split_tail = !m->keep && stage_terms(m, STAGE_BODY) == 0 && g_sdfa_gemm_variant == 0 && Mc / 256 >= 512 && g_sdfa_freq_proj_tail != 1;
+            if (split_tail) {
+                fat_grid = sdfa_fat_grid(256, Mc, sdfa_cu_count(), m->reserved_cus.load());
+                sa.fat_grid = (int)fat_grid; sa.tail_mode = g_sdfa_freq_proj_tail;
+            }
             pf.begin("share_map");
             if (table) {
                 sa.frame_clip = d_frame_clip + f0; sa.frame_start = d_frame_start + f0; sa.hop = hop;
@@ -206,7 +217,7 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
                 HIP_TRY(sdfa_launch_share_map_content(sa, s));
             }
             pf.end();
-            d_ulimit = sa.counts + 1; col_to_u = sa.col_to_u;
+            d_ulimit = sa.counts + 1; d_qfull = sa.counts + 2; col_to_u = sa.col_to_u;
             ca.col_src = sa.col_src; ca.col_limit = d_ulimit;
         }
         const int conv_terms = g_sdfa_conv_fp32 ? 0 : stage_terms(m, STAGE_BODY);
@@ -235,8 +246,14 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         g.bias = m->fp_b; g.q_tile_major = 1; g.q_slab_rows = HF_SLAB_ROWS;
         g.terms = stage_terms(m, STAGE_BODY);
         g.reserve_cus = m->reserved_cus.load();
-        if (share) { g.D = ws + w.ZU; g.q_limit = d_ulimit; }
-        pf.begin("freq_proj"); HIP_TRY(sdfa_launch_gemm(g, s)); pf.end();
+        if (share) { g.D = ws + w.ZU; g.q_limit = split_tail ? d_qfull : d_ulimit; }
+        pf.begin("freq_proj");
+        HIP_TRY(sdfa_launch_gemm(g, s));
+        if (split_tail) {      // columns [q_full, limit): at most fat_grid - 1 tiles, none when the rule declined
+            GemmTailArgs gt{m->fp_w, ws + w.HF, m->fp_b, ws + w.ZU, Mc, HF_SLAB_ROWS, d_qfull, d_ulimit, (int)fat_grid - 1};
+            HIP_TRY(sdfa_launch_gemm_tail(gt, s));
+        }
+        pf.end();
         // Column sharing reaches one stage further (round 4): the layer-0 input projection of the BiLSTM (rnn.py:20-21) is per column
         // too, so it runs over the DISTINCT columns and the layer-0 recurrence reads it through the share map -- the 256-feature
         // projection is then never expanded at all.  (fp32 kernels; the bf16 recurrences and the debug taps, which read the

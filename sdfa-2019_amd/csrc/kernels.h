@@ -214,14 +214,19 @@ struct ShareArgs {
     int32_t *tile_sum;           // [Mc/1024 + 1] scan scratch
     int32_t *col_src;            // [Mc] out: audio_feat row of each distinct column (-1 padding)
     int32_t *col_to_u;           // [Mc] out: distinct-column index of every column, in the index order above
-    int64_t *counts;             // [2]  out: number of distinct columns, and that rounded up to 256
+    int64_t *counts;             // [3]  out: [0] number of distinct columns; [1] that rounded up to 256 (the column limit of every stage);
+                                 // [2] q_full, where the persistent projection GEMM stops and sdfa_launch_gemm_tail starts (fat_grid)
     // sdfa_launch_share_map_content only (no frame table: prev / shift come from the features themselves)
     const float *feat;           // [N * 64][384] the chunk's audio_feat, one row per column
     uint64_t *hash;              // [N * 64] scratch: 64-bit hash of each column's bit pattern, frame-major
     uint64_t *linked;            // [N] scratch: bit t = column t of frame n has been compared in full with column t + shift[n] of frame prev[n], and is equal
+    // numbering (both fronts)
+    int fat_grid;                // workgroups G of the persistent projection GEMM behind this map: counts[2] = the whole rounds of G 256-column tiles
+                                 // when the tail rule (tail_mode 0; 2 = always) hands the rest to sdfa_launch_gemm_tail, else counts[2] = counts[1].  0 = no split
+    int tail_mode;
 };
 // All of a map's tables live in one int32 region: [counts: 16 words | prev | shift | owner | flag | uid | col_src | col_to_u | tile_sum].
-// (counts takes the first four of its 16 words; the front end keeps its stream kernel's status in word 8.)
+// (counts takes the first six of its 16 words; the front end keeps its stream kernel's status in word 8.)
 // sdfa_share_table_words is what that takes (tile_sum: one word per 1024 columns, share.hip: launch_share_numbering, and one to spare); a workspace
 // layout reserves at least that much, sdfa_share_carve (N / Nc / Mc set before) points the arguments into it.
 inline int64_t sdfa_share_table_words(int64_t Nc) { return 16 + 2 * Nc + 5 * (64 * Nc) + (64 * Nc) / 1024 + 1; }
@@ -235,6 +240,24 @@ hipError_t sdfa_launch_share_map(const ShareArgs &a, hipStream_t s);
 hipError_t sdfa_launch_share_map_content(const ShareArgs &a, hipStream_t s);   // the same map, built from the contents of audio_feat (t_lo / t_hi / frame_clip / frame_start / hop unused)
 hipError_t sdfa_launch_share_prev(const ShareArgs &a, hipStream_t s);     // prev / shift only (the spectral-stream front end reads the chains from them)
 hipError_t sdfa_launch_expand_cols(const float *Zu, const int32_t *col_to_u, float *Z, int nquads, int64_t Mc, hipStream_t s);
+
+// Tail of the shared-column frequency projection (gemm_tail.hip): columns [*q_lo, *q_hi) -- device scalars, multiples of 256 -- of
+//   D[p][q] = sum_k P[k][p] * Q[k][q] + bias[p]      fp32, K4 output, 256 rows, Q in the tile-major hidden-state layout, K = 8192,
+// in 64 x 64 blocks, bit for bit what gemm_fat_kernel stores for them.  The grid covers max_tiles 256-column tiles; workgroups past *q_hi exit.
+struct GemmTailArgs {
+    const float *P, *Q, *bias;
+    float *D;
+    int64_t ldd;
+    int q_slab_rows;
+    const int64_t *q_lo, *q_hi;
+    int max_tiles;
+};
+hipError_t sdfa_launch_gemm_tail(const GemmTailArgs &a, hipStream_t s);
+// workgroups of gemm_fat_kernel for a K4 product of `rows` x `cols` (gemm.hip: launch_fat)
+inline int64_t sdfa_fat_grid(int64_t rows, int64_t cols, int cus, int reserve_cus) {
+    const int64_t ntiles = (rows / 256) * (cols / 256), wgs = cus - reserve_cus > 1 ? cus - reserve_cus : 1;
+    return ntiles < wgs ? ntiles : wgs;
+}
 
 // ---- dgrad -> mesh (mesh.hip) -----------------------------------------------------------------------
 struct MeshArgs {

@@ -241,6 +241,8 @@ __global__ __launch_bounds__(1024) void share_scan_tiles_kernel(ShareArgs a) {
     if (threadIdx.x == 1023) a.tile_sum[blockIdx.x] = inc;
 }
 
+// the tail rule (below): split while (T mod G) / G <= TAIL_NUM / TAIL_DEN
+constexpr int TAIL_NUM = 3, TAIL_DEN = 4;
 __global__ __launch_bounds__(1024) void share_scan_sums_kernel(ShareArgs a, int ntiles) {
     __shared__ int part[1024];
     int carry = 0;
@@ -256,6 +258,16 @@ __global__ __launch_bounds__(1024) void share_scan_sums_kernel(ShareArgs a, int 
         const int64_t mu = carry, pad = (mu + 255) / 256 * 256;
         a.counts[0] = mu;
         a.counts[1] = pad;
+        // The projection GEMM behind this map is persistent, fat_grid = G workgroups over T = pad / 256 column tiles: T mod G tiles
+        // left over cost it a whole round.  It stops at q_full, the whole rounds, and the tail kernel (gemm_tail.hip) multiplies the
+        // r = T mod G tiles behind -- when that is the cheaper way.  Measured at G = 256 (profiles/encoder_tail_ab.txt): a round of the
+        // fat kernel 1.80 ms, the tail kernel 0.20 ms + 7.9 us per tile -- 1.71 ms at r = 192, 2.0 ms at r = 224.
+        int64_t q_full = pad;
+        if (a.fat_grid > 0 && a.tail_mode != 1) {
+            const int64_t T = pad / 256, G = a.fat_grid, r = T % G;
+            if (a.tail_mode == 2 || r * TAIL_DEN <= G * TAIL_NUM) q_full = (T - r) * 256;
+        }
+        a.counts[2] = q_full;
     }
 }
 
