@@ -209,8 +209,9 @@ int64_t sdfa_workspace_status(const void *d_workspace, int word, void *stream);
  *
  * The per-column stages (conv stack, frequency LSTM, its projection, the layer-0 input projection) are evaluated once per
  * DISTINCT column: overlapping analysis windows hold bit-identical columns, and the call finds them in d_audio_feat itself, per
- * workspace chunk, on every call -- a 64-bit hash per column proposes pairs among the 64 preceding frames, and a pair is shared
- * only after its 384 words have been compared in full as bit patterns.  The rows are bitwise those of evaluating every column
+ * workspace chunk, on every call -- a 64-bit hash per column groups the chunk's columns, wherever in the chunk they are, and a column
+ * shares its group's first column only after the two columns' 384 words have been compared in full as bit patterns: exactly the
+ * distinct bit patterns of a chunk are evaluated.  The rows are bitwise those of evaluating every column
  * ("encoder_dedup_off" = 1 does that; sdfa_debug_keep_intermediates models always do).  Features without copies cost the scan only.
  * ---------------------------------------------------------------------------------------- */
 int sdfa_encoder_forward(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames,
@@ -311,6 +312,9 @@ int sdfa_ensemble_mean(const float *d_a, const float *d_b, int64_t n, float *d_o
  *   "encoder_dedup_off" 1 = sdfa_encoder_forward (no frame table) evaluates every column of every frame, as it did before it learnt to find the
  *                      identical columns of audio_feat itself (hash, then a full bit-pattern compare of every proposed pair, on the device, on
  *                      every call); the every-column path is the reference the sharing tests compare against.  Same bits
+ *   "share_hash_bits"  n in 1..32 = that scan groups the columns by the n low bits of its 64-bit hash only (0 = by all of them), so that columns of
+ *                      different content meet in one group and the full compare has to refuse them (tests).  Same bits; a refused column is
+ *                      evaluated on its own, so more columns are evaluated than there are distinct ones
  *   "freq_proj_tail"   the shared-column frequency projection (fp32, chunks of 2,048 frames and more): the column tiles behind the last whole
  *                      round of the persistent GEMM's grid go to a fine-tile kernel (gemm_tail.hip) instead of costing a round of their own.
  *                      0 = where the device-side rule says it pays (default), 1 = never (one launch, as before), 2 = always.  Same bits

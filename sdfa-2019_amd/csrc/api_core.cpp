@@ -46,6 +46,7 @@ thread_local int g_sdfa_time_lstm_handoff = 0;
 thread_local int g_sdfa_time_lstm_timeout_us = 0;
 thread_local int g_sdfa_share_gx0_off = 0;
 thread_local int g_sdfa_encoder_dedup_off = 0; // "encoder_dedup_off": 1 = sdfa_encoder_forward evaluates every column (no scan of audio_feat for identical columns)
+thread_local int g_sdfa_share_hash_bits = 0;  // "share_hash_bits" (tests): the encoder's column scan groups by the low n bits of its 64-bit hash only (0 = all of them), so that hashes collide and the full compare decides
 thread_local int g_sdfa_freq_proj_tail = 0;   // "freq_proj_tail": the shared-column frequency projection's last partial round of gemm_fat_kernel in fine tiles (gemm_tail.hip): 0 = where the device-side rule says it pays, 1 = never, 2 = always
 thread_local int g_sdfa_attn_unfused = 0;  // "attn_unfused": 1 = the bf16 attention modes keep the three-GEMM + attn_kernel form of round 5 (A/B)
 
@@ -62,6 +63,7 @@ int sdfa_debug_set_option(const char *name, int value) {
         {"attn_unfused", &g_sdfa_attn_unfused},
         {"share_gx0_off", &g_sdfa_share_gx0_off},
         {"encoder_dedup_off", &g_sdfa_encoder_dedup_off},
+        {"share_hash_bits", &g_sdfa_share_hash_bits, 0, 32, "0 (the whole hash) or 1..32 low bits"},
         {"freq_proj_tail", &g_sdfa_freq_proj_tail, 0, 2, "0 (rule), 1 (never) or 2 (always)"},
         {"frontend_two_kernel", &g_sdfa_frontend_two_kernel},
         {"frontend_stream_phases", &g_sdfa_frontend_stream_phases},

@@ -9,7 +9,7 @@
 
 // A/B options this file reads (api_core.cpp)
 extern thread_local int g_sdfa_gemm_variant, g_sdfa_freq_lstm_shape, g_sdfa_pca_lds, g_sdfa_pca_fp32, g_sdfa_conv_fp32, g_sdfa_share_gx0_off, g_sdfa_attn_unfused, g_sdfa_encoder_dedup_off,
-    g_sdfa_freq_proj_tail;
+    g_sdfa_freq_proj_tail, g_sdfa_share_hash_bits;
 
 // ================================================================================================
 // workspace layout (floats), per chunk of Nc frames, Mc = 64*Nc columns
@@ -210,10 +210,13 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
                 sa.t_lo = 6; sa.t_hi = 58;      // feature columns: see share.hip
                 HIP_TRY(sdfa_launch_share_map(sa, s));
             } else {
-                // scratch of the scan (2 Mc + 2 Nc words): the head of the frequency LSTM's hidden-state region, which nobody has written
-                // yet in this chunk (the conv stack writes X3; the frequency LSTM is HF's first writer) and which is 8192 Mc words long
+                // scratch of the scan (hashes + the group table, under 14 Mc words): the head of the frequency LSTM's hidden-state region, which
+                // nobody has written yet in this chunk (the conv stack writes X3; the frequency LSTM is HF's first writer) and which is 8192 Mc words long
                 sa.feat = ca.audio_feat;
-                sa.hash = reinterpret_cast<uint64_t *>(ws + w.HF); sa.linked = sa.hash + Mc;
+                sa.hash = reinterpret_cast<uint64_t *>(ws + w.HF);
+                sa.group_slots = sdfa_share_group_slots(N);
+                sa.group_key = sa.hash + Mc; sa.group_first = reinterpret_cast<uint32_t *>(sa.group_key + sa.group_slots);
+                sa.hash_bits = g_sdfa_share_hash_bits;
                 HIP_TRY(sdfa_launch_share_map_content(sa, s));
             }
             pf.end();

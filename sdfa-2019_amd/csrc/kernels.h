@@ -216,10 +216,13 @@ struct ShareArgs {
     int32_t *col_to_u;           // [Mc] out: distinct-column index of every column, in the index order above
     int64_t *counts;             // [3]  out: [0] number of distinct columns; [1] that rounded up to 256 (the column limit of every stage);
                                  // [2] q_full, where the persistent projection GEMM stops and sdfa_launch_gemm_tail starts (fat_grid)
-    // sdfa_launch_share_map_content only (no frame table: prev / shift come from the features themselves)
+    // sdfa_launch_share_map_content only (no frame table: the owners come from the features themselves; prev / shift unused)
     const float *feat;           // [N * 64][384] the chunk's audio_feat, one row per column
     uint64_t *hash;              // [N * 64] scratch: 64-bit hash of each column's bit pattern, frame-major
-    uint64_t *linked;            // [N] scratch: bit t = column t of frame n has been compared in full with column t + shift[n] of frame prev[n], and is equal
+    uint64_t *group_key;         // [group_slots] scratch: open-addressing table of the chunk's hashes, stored complemented (all ones = empty slot)
+    uint32_t *group_first;       // [group_slots] scratch: smallest column index (index order above) among the columns with the slot's hash
+    int64_t group_slots;         // sdfa_share_group_slots(N)
+    int hash_bits;               // "share_hash_bits": 0 = the whole hash, 1..32 = only that many low bits of it (tests: forces collisions)
     // numbering (both fronts)
     int fat_grid;                // workgroups G of the persistent projection GEMM behind this map: counts[2] = the whole rounds of G 256-column tiles
                                  // when the tail rule (tail_mode 0; 2 = always) hands the rest to sdfa_launch_gemm_tail, else counts[2] = counts[1].  0 = no split
@@ -230,6 +233,9 @@ struct ShareArgs {
 // sdfa_share_table_words is what that takes (tile_sum: one word per 1024 columns, share.hip: launch_share_numbering, and one to spare); a workspace
 // layout reserves at least that much, sdfa_share_carve (N / Nc / Mc set before) points the arguments into it.
 inline int64_t sdfa_share_table_words(int64_t Nc) { return 16 + 2 * Nc + 5 * (64 * Nc) + (64 * Nc) / 1024 + 1; }
+// Slots of the content front's hash table: a power of two, at least twice the chunk's real columns (so a probe sequence always ends).  The
+// front's scratch is hash | group_key | group_first = 2 * 64 N + 3 * slots words, less than 14 Mc.
+inline int64_t sdfa_share_group_slots(int64_t N) { int64_t s = 1024; while (s < 2 * 64 * N) s <<= 1; return s; }
 inline void sdfa_share_carve(ShareArgs &a, int32_t *base) {
     a.counts = reinterpret_cast<int64_t *>(base);
     a.prev = base + 16; a.shift = a.prev + a.Nc;

@@ -12,20 +12,23 @@
 //     caller has one -- the argument above is then the proof that the linked columns are equal;
 //   * the contents of audio_feat (sdfa_launch_share_map_content), where it has not (sdfa_encoder_forward).  Nothing
 //     is assumed about where the features came from: a column is linked to another only after the two columns'
-//     384 words have been compared in full, as bit patterns (-0.0 != +0.0, NaNs by payload).  Four kernels:
-//       share_hash_kernel     one streaming pass: a 64-bit hash of every column.  Hashes only PROPOSE.
-//       share_match_kernel    per frame n, the earlier frame p = n - b (b <= 64, same chunk) and shift d >= 1 for
-//                             which the most columns' hashes agree, hash(n, t) == hash(p, t + d): the table's
-//                             prev / shift (frames 12 back, d = 25 at 16 kHz / 60 fps) without the table.  The
-//                             table's own (p, d) is among the candidates, so on front-end features this front links
-//                             at least as many columns per frame as the table does (53 - d of them), and the number
-//                             of distinct columns -- the columns without a link -- is at most the table's.
-//       share_verify_kernel   every proposed pair (n, t) ~ (p, t + d) with equal hashes is read and compared word
-//                             for word; only a pair that passes gets its bit in linked[n].
-//       share_owner_content_kernel  follows verified links to the canonical column.  A step goes to an earlier
-//                             frame and a LATER time step (d >= 1, t + d <= 63), so a walk ends within 63 steps
-//                             whatever the data (an all-zero chunk links every (n, t) to (n - 1, t + 1)).
-//     Equality is transitive, so a chain of verified links is sound; a copy that is not found costs time only.
+//     384 words have been compared in full, as bit patterns (-0.0 != +0.0, NaNs by payload).  All bit-equal columns of
+//     the chunk go under ONE owner, wherever in the chunk they are -- there is no search over frames and shifts:
+//       share_hash_kernel     one streaming pass: a 64-bit hash of every column, and in its tail the column's entry
+//                             in an open-addressing table of the chunk's hashes (cleared by a memset before): the
+//                             slot of a hash keeps the smallest column index (index order: col_index below) that
+//                             carries it.  Hashes only PROPOSE, and a minimum does not depend on the order in which
+//                             the atomics land: the map is the same on every run.
+//       share_resolve_kernel  every column looks its hash up.  The column the slot names is an owner; any other
+//                             column is read and compared word for word with that owner, and is linked to it only
+//                             if the compare passes.  One that fails (two contents, one hash) stays its own owner,
+//                             as do the other columns of its content: a collision costs time only.
+//     Links are one level deep, so nothing is walked, and the owner of a group is its first column in index order:
+//     on front-end features the distinct columns are those of the frame table's map or fewer (zero-padded columns
+//     at a clip's ends and copies further than 64 frames apart are grouped too).  What the mapped layer-0 recurrence
+//     (lstm.hip: time_lstm_body, MAP) then reads: the 32 frames of a half-wave at one time step are a few runs of
+//     consecutive distinct columns, or -- zero padding, silence -- one and the same column, so a request stays a few 128-byte lines and a tile with a clip's
+//     end in it reads no more lines than an interior one (profiles/encoder_group_ab.txt: lstm0).
 #include "common.h"
 #include "kernels.h"
 
@@ -88,6 +91,7 @@ __global__ void share_owner_kernel(ShareArgs a) {
 // A column is 384 words = 96 16-byte quads = 1,536 contiguous bytes of audio_feat.  The hash and the full compare give a
 // column to a half-wave: lane l of the half reads quads l, l + 32, l + 64, so a wave's load covers two adjacent columns.
 constexpr int COL_QUADS = 96;
+constexpr unsigned long long GROUP_EMPTY = ~0ull;
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 32; x *= 0xd6e8feb86659fd93ull;
@@ -95,7 +99,11 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     return x ^ (x >> 32);
 }
 
-// hash[n * 64 + t] = sum over the column's quads of a mix of (quad bits, quad position): one coalesced pass over the chunk
+// hash[n * 64 + t] = sum over the column's quads of a mix of (quad bits, quad position): one coalesced pass over the chunk.  The lane
+// that stores a column's hash also enters it in the group table: group_key holds the complement of a slot's hash (a hash is never 0, so
+// the memset's all-ones word is an empty slot and no key), group_first the smallest column index with that hash.  Both only ever move
+// one way (empty -> key, index downwards), so a plain look first spares the atomic where it would change nothing -- in a chunk of equal
+// columns that is nearly every one of them -- and a stale look only costs the atomic it could have spared.
 __global__ __launch_bounds__(256) void share_hash_kernel(ShareArgs a) {
     const int l = threadIdx.x & 31;
     const int64_t col = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5, M = a.N * 64;
@@ -111,110 +119,67 @@ __global__ __launch_bounds__(256) void share_hash_kernel(ShareArgs a) {
         }
     }
     for (int off = 16; off; off >>= 1) h += __shfl_xor(h, off);      // offsets < 32: stays inside the half-wave
-    if (col < M && l == 0) a.hash[col] = mix64(h) | 1;              // never 0: 0 marks an empty slot of share_match_kernel's table
+    h = mix64(h);
+    if (a.hash_bits) h &= (1ull << a.hash_bits) - 1;
+    h |= 1;                                                          // never 0
+    // A workgroup's 8 columns are consecutive time steps of one frame (the grid is exact: col < M).  Of those with one hash only the first,
+    // which has the smallest index of them in either order, goes to the table: in a chunk of equal columns, where every column of the
+    // chunk meets on one slot before the first key is seen there, that is an eighth of the atomics on that one address.
+    __shared__ unsigned long long wg_hash[8];
+    const int c = threadIdx.x >> 5;
+    if (l == 0) { a.hash[col] = h; wg_hash[c] = h; }
+    __syncthreads();
+    if (l) return;
+    for (int j = 0; j < c; ++j)
+        if (wg_hash[j] == h) return;
+    const unsigned long long key = ~h;
+    const unsigned i = (unsigned)col_index(a, col >> 6, (int)(col & 63));
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(a.group_key);
+    const int64_t mask = a.group_slots - 1;
+    for (int64_t slot = (int64_t)(h >> 1) & mask, k = 0; k <= mask; ++k, slot = (slot + 1) & mask) {     // the table is at most half full
+        unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == GROUP_EMPTY) {
+            cur = atomicCAS(&keys[slot], GROUP_EMPTY, key);
+            if (cur == GROUP_EMPTY) cur = key;
+        }
+        if (cur != key) continue;
+        if (__hip_atomic_load(&a.group_first[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > i) atomicMin(&a.group_first[slot], i);
+        break;
+    }
 }
 
-// prev[n] / shift[n] = the (p, d), n - 64 <= p < n, 1 <= d <= 63, with the most t for which hash(n, t) == hash(p, t + d); ties go to the
-// nearest frame, then to the smallest shift; prev = -1 when no hash of the frame reappears.  One wave per frame.  Most earlier frames
-// hold no column of frame n at all (at 60 fps / hop 128 only every twelfth is hop-aligned with it), so the frame's 64 hashes go into
-// a small open-addressing table in LDS first and a frame p is looked at further only if one of its hashes is in the table.  For such
-// a p, lane tt holds hash(p, tt) and compares it with hash(n, tt - d) from LDS, for every d that could still beat the best so far (a
-// shift of d has only 64 - d columns to offer, so the loop shrinks as soon as a good pair is known -- at once, in a chunk of equal
-// columns).
-constexpr int MATCH_SLOTS = 128;      // twice the keys: a probe sequence ends at an empty slot after at most 64 occupied ones
-__global__ __launch_bounds__(256) void share_match_kernel(ShareArgs a) {
-    __shared__ unsigned long long hn[4][64], tab[4][MATCH_SLOTS];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t n = (int64_t)blockIdx.x * 4 + w;
-    const bool real = n < a.N && n > 0;                              // wave-uniform
-    const unsigned long long mine = real ? a.hash[n * 64 + lane] : 1;
-    hn[w][lane] = mine;
-    tab[w][lane] = 0; tab[w][lane + 64] = 0;
-    __syncthreads();
-    for (int slot = (int)(mine >> 8) & (MATCH_SLOTS - 1), k = 0; k < MATCH_SLOTS; ++k, slot = (slot + 1) & (MATCH_SLOTS - 1)) {
-        const unsigned long long old = atomicCAS(&tab[w][slot], 0ull, mine);
-        if (old == 0 || old == mine) break;                          // mine now, or an equal column of this frame got there first
+// owner / flag as share_owner_kernel writes them.  A column to a half-wave, as above; the column that its hash's slot names is an owner, any
+// other is compared in full with that one.  Padding frames own nothing.
+__global__ __launch_bounds__(256) void share_resolve_kernel(ShareArgs a) {
+    const int l = threadIdx.x & 31, half = (threadIdx.x & 63) >> 5;
+    const int64_t col = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5, n = col >> 6;       // col < 64 Nc: the grid is exact
+    const int64_t i = col_index(a, n, (int)(col & 63));
+    if (n >= a.N) {                                                  // wave-uniform: a wave's two columns are of one frame
+        if (l == 0) { a.owner[i] = -1; a.flag[i] = 0; }
+        return;
     }
-    __syncthreads();
-    if (n >= a.Nc) return;
-    int best = 0, bp = -1, bd = 0;
-    if (real) {
-        const int64_t lo = n > 64 ? n - 64 : 0;
-        unsigned long long hp = a.hash[(n - 1) * 64 + lane];
-        for (int64_t p = n - 1; p >= lo && best < 63; --p) {
-            const unsigned long long hq = p > lo ? a.hash[(p - 1) * 64 + lane] : 0;      // next frame's hashes: in flight during this one's work
-            bool member = false;
-            for (int slot = (int)(hp >> 8) & (MATCH_SLOTS - 1), k = 0; k < MATCH_SLOTS; ++k, slot = (slot + 1) & (MATCH_SLOTS - 1)) {
-                const unsigned long long v = tab[w][slot];
-                if (v == hp) member = true;
-                if (v == hp || v == 0) break;
-            }
-            if (__ballot(member)) {
-                for (int d0 = 1; d0 < 64 - best; d0 += 4) {          // four shifts per round: independent LDS reads
-                    int c[4];
+    const uint64_t h = a.hash[col], mask = (uint64_t)a.group_slots - 1;
+    uint64_t slot = (h >> 1) & mask;
+    for (uint64_t k = 0; k < mask && a.group_key[slot] != ~h; ++k) slot = (slot + 1) & mask;   // it is there: share_hash_kernel put it
+    const int64_t cand = a.group_key[slot] == ~h ? (int64_t)a.group_first[slot] : i;           // (were it not, the column would own itself: no index is read from an empty slot)
+    bool differ = false;
+    if (cand != i) {
+        int64_t cn;
+        int ct;
+        col_of(a, cand, cn, ct);
+        const uint4 *x = reinterpret_cast<const uint4 *>(a.feat) + col * COL_QUADS, *y = reinterpret_cast<const uint4 *>(a.feat) + (cn * 64 + ct) * COL_QUADS;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int d = d0 + k;
-                        const bool eq = lane >= d && hn[w][lane >= d ? lane - d : 0] == hp;       // d > 63: no lane, count 0
-                        c[k] = __popcll(__ballot(eq));
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (c[k] > best) { best = c[k]; bp = (int)p; bd = d0 + k; }
-                }
-            }
-            hp = hq;
+        for (int k = 0; k < 3; ++k) {
+            const uint4 u = x[l + 32 * k], v = y[l + 32 * k];
+            differ |= ((u.x ^ v.x) | (u.y ^ v.y) | (u.z ^ v.z) | (u.w ^ v.w)) != 0;
         }
     }
-    if (lane == 0) { a.prev[n] = bp; a.shift[n] = bd; }
-}
-
-// linked[n] bit t = columns (n, t) and (prev[n], t + shift[n]) hold the same 384 words.  Only pairs whose hashes agree are read; every
-// such pair is read in full.  One workgroup per frame, 16 columns per wave, two columns (one per half-wave) per step.
-__global__ __launch_bounds__(256) void share_verify_kernel(ShareArgs a) {
-    const int64_t n = blockIdx.x;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, half = lane >> 5, l = lane & 31;
-    const int p = a.prev[n], d = a.shift[n];
-    unsigned bits = 0;                                               // wave-uniform: the verdicts of columns 16 w .. 16 w + 15
-    if (p >= 0) {
-        const uint64_t *hn = a.hash + n * 64, *hp = a.hash + (int64_t)p * 64;
-        const uint4 *fn = reinterpret_cast<const uint4 *>(a.feat) + n * 64 * COL_QUADS;
-        const uint4 *fp = reinterpret_cast<const uint4 *>(a.feat) + (int64_t)p * 64 * COL_QUADS;
-        for (int j = 0; j < 8; ++j) {
-            const int t = 16 * w + 2 * j + half, tt = t + d;
-            const bool cand = tt < 64 && hn[t] == hp[tt];           // uniform over the half-wave
-            bool differ = false;
-            if (cand) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const uint4 x = fn[t * COL_QUADS + l + 32 * k], y = fp[tt * COL_QUADS + l + 32 * k];
-                    differ |= ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) != 0;
-                }
-            }
-            const uint64_t c = __ballot(cand), bad = __ballot(differ);
-            if ((c & 1) && !(bad & 0xffffffffull)) bits |= 1u << (2 * j);
-            if ((c >> 32 & 1) && !(bad >> 32)) bits |= 1u << (2 * j + 1);
-        }
+    const uint64_t bad = __ballot(differ) >> (32 * half) & 0xffffffffull;
+    if (l == 0) {
+        const int64_t o = bad ? i : cand;
+        a.owner[i] = (int)o;
+        a.flag[i] = o == i ? 1 : 0;
     }
-    if (lane == 0) reinterpret_cast<uint16_t *>(a.linked)[n * 4 + w] = (uint16_t)bits;     // little-endian: bits 16 w .. 16 w + 15 of linked[n]
-}
-
-// owner / flag as share_owner_kernel writes them, from the verified links.  A set bit t of linked[n] implies t + shift[n] <= 63 and
-// shift[n] >= 1 (share_match_kernel, share_verify_kernel), so t grows with every step: the walk is over within 63 steps for any input.
-__global__ void share_owner_content_kernel(ShareArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.Mc) return;
-    int64_t n;
-    int t;
-    col_of(a, i, n, t);
-    if (n >= a.N) { a.owner[i] = -1; a.flag[i] = 0; return; }     // padding frame: never computed
-    while (t < 63 && (a.linked[n] >> t & 1)) {
-        t += a.shift[n];
-        n = a.prev[n];
-    }
-    const int64_t o = col_index(a, n, t);
-    a.owner[i] = (int)o;
-    a.flag[i] = o == i ? 1 : 0;
 }
 
 // Exclusive scan of flag[0..Mc) -> uid in three small launches: per-tile (1024 columns) scan + tile sums, a
@@ -313,10 +278,10 @@ static void launch_share_numbering(const ShareArgs &a, hipStream_t s) {
 }
 
 hipError_t sdfa_launch_share_map_content(const ShareArgs &a, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(a.group_key, 0xff, (size_t)a.group_slots * 12, s);      // group_key | group_first: every slot empty, no index yet
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(share_hash_kernel, dim3((unsigned)(a.N * 8)), dim3(256), 0, s, a);       // 8 columns per workgroup, 64 per frame
-    hipLaunchKernelGGL(share_match_kernel, dim3((unsigned)(a.Nc / 4)), dim3(256), 0, s, a);     // Nc is a multiple of 128
-    hipLaunchKernelGGL(share_verify_kernel, dim3((unsigned)a.N), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(share_owner_content_kernel, dim3((unsigned)((a.Mc + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(share_resolve_kernel, dim3((unsigned)(a.Nc * 8)), dim3(256), 0, s, a);
     launch_share_numbering(a, s);
     return hipGetLastError();
 }
