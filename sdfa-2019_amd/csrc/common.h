@@ -88,6 +88,26 @@ __device__ __forceinline__ float tanhf_acc(float x) {
     return copysignf((1.0f - e) * fast_rcp(1.0f + e), x);
 }
 
+// Split of eight floats into NPL bf16 planes, the operand octets of v_mfma_f32_32x32x16_bf16: pl[0] = bf16(x), pl[1] = bf16(x - pl[0]),
+// pl[2] = bf16(x - pl[0] - pl[1]) (both differences are exact in fp32); planes NPL.. are left untouched.  conv.hip and pca.hip split
+// with this.  lstm.hip (split_octet, split_octet3), attn.hip (ks_split8) and gemm.hip (split8) still carry copies of the same arithmetic:
+// their sha1 keys the committed counter records, so they move here with the next counter re-collection.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+template <int NPL>
+__device__ __forceinline__ void bf16_split(const float (&x)[8], bf16x8 (&pl)[3]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const __bf16 hb = (__bf16)x[e];
+        pl[0][e] = hb;
+        if (NPL > 1) {
+            const float r1 = x[e] - (float)hb;
+            const __bf16 mb = (__bf16)r1;
+            pl[1][e] = mb;
+            if (NPL > 2) pl[2][e] = (__bf16)(r1 - (float)mb);
+        }
+    }
+}
+
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
 

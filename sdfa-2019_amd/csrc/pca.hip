@@ -143,12 +143,9 @@ constexpr int PB_SLAB = 2 * (12 * 192 + 24 * 96);      // octets per triangle bl
 
 __device__ __forceinline__ void pca_split(const float4 &x0, const float4 &x1, pbf16x8 &hi, pbf16x8 &lo) {
     const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 hb = (__bf16)x[e];
-        hi[e] = hb;
-        lo[e] = (__bf16)(x[e] - (float)hb);
-    }
+    pbf16x8 pl[3];
+    bf16_split<2>(x, pl);
+    hi = pl[0]; lo = pl[1];
 }
 
 template <bool BF>

@@ -284,6 +284,26 @@ def test_fused_conv_stack_is_bitwise_the_two_kernel_path(eng, synth_sd, golden):
     assert torch.equal(z0, z2)
 
 
+@pytest.fixture(scope="module")
+def eng_fused(synth_sd):
+    return Engine(synth_sd["dgrad"])
+
+
+@pytest.mark.parametrize("n", [1, 33, 130])
+def test_two_kernel_conv_path_is_bitwise_the_fused_one_at_small_sizes(eng, eng_fused, n):
+    """conv1_pool + conv23 (`eng` keeps intermediates) against conv123_kernel (`eng_fused`), both built from the stage functions
+    of conv.hip, on dense random features where no two columns are equal: one 32-column tile per time step (n = 1), a partial
+    second tile (33), more than one 128-frame pad (130).  Every workgroup grid has the chunks fc = 0 and 7, i.e. the halo rows
+    f1 = -1 and 64, and the padding columns are zeroed by both stagings.  Compared through z and align: a keep-intermediates
+    engine never launches the fp32 fused kernel (with the option conv_fp32 = 1 it takes the two-kernel branch as well), and an
+    engine without intermediates has no taps, so X3 of the two paths cannot be read from one engine."""
+    x = torch.rand((n, 64, 128, 3), generator=torch.Generator().manual_seed(100 + n)).cuda()
+    z0, a0 = eng.encoder(x)
+    z1, a1 = eng_fused.encoder(x)
+    assert torch.isfinite(z0).all() and float(z0.abs().max()) > 0
+    assert torch.equal(z0, z1) and torch.equal(a0, a1)
+
+
 def test_pca_forms_are_bitwise_identical(synth_sd):
     """The two forms of the dgrad PCA expansion -- pca_dgrad_res_kernel (default: basis slab resident in LDS, persistent work
     units, padded k-blocks skipped) and pca_dgrad_kernel (the two-workgroups-per-CU fallback: every wave fetches the slab itself)

@@ -13,7 +13,7 @@ from sdfa_amd import synth
 from sdfa_amd.engine import Engine
 res = {}
 for head in ("dgrad", "offsets"):
-    for prec in ("fp32", "bf16x3"):
+    for prec in ("fp32", "bf16x3", "bf16x6", "bf16"):
         eng = Engine(synth.make_state_dict(head, 1234), max_frames=2048, precision=prec)
         torch.manual_seed(5)
         x = torch.rand((700, 64, 128, 3), device="cuda")
