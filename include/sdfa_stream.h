@@ -28,6 +28,18 @@
  *
  * A step costs one host -> device copy (new samples + segment table + frame table), sdfa_stream_ring_append and
  * sdfa_mel_frontend_ring, whatever the number of streams; the encoder and the regressor are the sdfa_hip.h calls.
+ *
+ * Capture-rate streams.  A stream may arrive at another rate than the model's (44.1 kHz, 48 kHz, ...).  Its samples are appended
+ * to an INPUT ring (a second ring array with its own r_in, filled by sdfa_stream_ring_append) and sdfa_stream_resample converts
+ * them into the stream's model ring with the arithmetic of sdfa_resample (sdfa_hip.h), one float32 multiply by a gain and a
+ * clamp to +-0.999 on the store.  With tr(t) the time register of output t (0 for t = 0, += 1 / ratio per output, accumulated
+ * sequentially in float64), n = int(tr(t)) and wing(t) = (nwin - offset) / step the taps of its right wing, output t is FINAL
+ * after n_in received samples when n(t') + 1 + wing(t') <= n_in for every t' <= t: its right wing is complete and later samples
+ * cannot change it.  A step converts exactly the final outputs not yet produced, and their count is the stream's model-rate
+ * length for the frame rule above; when the stream ends after n_in samples the outputs up to int(n_in * ratio) are produced
+ * with the truncated wings of the offline call, zeros follow up to ceil(n_in * ratio), and that is its model-rate length.  The
+ * model ring then holds, position by position, clip(sdfa_resample(whole signal) * gain, -0.999, 0.999).  The input ring must
+ * keep [n(t) - wing, n_in) for the first output t not yet produced: R_in >= 2 (nwin / step + 1) + samples between two steps + 1.
  */
 #ifndef SDFA_STREAM_H
 #define SDFA_STREAM_H
@@ -40,6 +52,7 @@ extern "C" {
 
 #define SDFA_STREAM_ABI_VERSION 1
 #define SDFA_STREAM_RING_MIRROR 2048   /* floats repeated behind each ring: >= win + 2 at 8 and 16 kHz */
+#define SDFA_STREAM_MAX_RATES 8        /* distinct input rates one sdfa_stream_resample call takes */
 
 int sdfa_stream_abi_version(void);
 
@@ -77,6 +90,37 @@ int sdfa_stream_ring_append(float *d_rings, int r, int32_t n_rings, const int64_
 int sdfa_mel_frontend_ring(const float *d_rings, int r, int32_t n_rings, const int64_t *d_view_ring, const int64_t *d_view_hi,
                            int32_t n_views, const int32_t *d_frame_view, const int64_t *d_frame_start, int64_t n_frames,
                            int sample_rate, float *d_audio_feat, void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* Number of FINAL outputs of a stream at sr_in that has received n_in samples, at the model rate sr_out (the rule above); n_in when
+ * the rates are equal.  Host only.  A rate pair that sdfa_resample refuses returns SDFA_EINVAL with its message. */
+int64_t sdfa_stream_resample_final(int64_t n_in, int sr_in, int sr_out);
+
+/* Time registers of `count` consecutive outputs: h_treg[i] (may be NULL) = the register of the i-th of them, *h_state = the register
+ * of the first on entry (0.0 for output 0) and of the one after the last on return.  The sequential float64 accumulation of
+ * sdfa_resample, so the register is a function of the output index alone however the calls are cut.  Host only.  Returns count. */
+int64_t sdfa_stream_resample_register(int64_t count, int sr_in, int sr_out, double *h_state, double *h_treg);
+
+/* Lengths of a stream that ended after n_in samples: returns n_out = sdfa_resample_out_len, *h_n_res = the outputs that are filtered
+ * (zeros from there to n_out).  The refusals of sdfa_resample with their messages ("too small to resample").  Host only. */
+int64_t sdfa_stream_resample_close(int64_t n_in, int sr_in, int sr_out, int64_t *h_n_res);
+
+/* nwin / step of a rate pair: no wing of an output reaches further than this many input samples (+ 1 on the left, the sample at
+ * n itself); 0 when the rates are equal.  Host only; the refusals of sdfa_resample_final. */
+int64_t sdfa_stream_resample_wing(int sr_in, int sr_out);
+
+/* Input rings -> model rings, every stream of a step in one launch.  d_seg holds n_seg segments of eight int64:
+ *   input ring, model ring, t0, count, n_in, t_zero, offset in d_treg, rate index | (float32 bits of the gain) << 32
+ * Segment j writes outputs t0 .. t0 + count - 1 of its stream to its model ring (each at t & (2^r - 1), and into the mirror when
+ * that is below SDFA_STREAM_RING_MIRROR): zeros for t < 0 (the zeros ahead of an ensembling stream) and for t >= t_zero (pass n_res
+ * once the stream has ended, INT64_MAX before), else the resampled sample from the n_in samples received so far, times the gain,
+ * clamped.  d_treg[offset + i] is the register of output max(t0, 0) + i (sdfa_stream_resample_register), for the outputs below
+ * t_zero.  h_rates (HOST) lists the n_rates <= SDFA_STREAM_MAX_RATES input rates the segments index; a rate equal to sr_out copies.
+ * max_count >= every segment's count.  A segment with an index, count or register range outside its array is skipped.  Outputs
+ * must be final (or the stream ended), and [n(t0) - wing, n_in) still in the input ring.  Never synchronises -- except that the
+ * first call with a rate pair on a device builds and uploads that pair's filter table (sdfa_resample shares the tables). */
+int sdfa_stream_resample(const float *d_in_rings, int r_in, int32_t n_in_rings, float *d_rings, int r, int32_t n_rings, const int64_t *d_seg,
+                         int32_t n_seg, int64_t max_count, const double *d_treg, int64_t n_treg, const int32_t *h_rates, int32_t n_rates,
+                         int sr_out, void *stream);
 
 #ifdef __cplusplus
 }

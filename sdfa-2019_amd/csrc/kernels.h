@@ -319,3 +319,22 @@ struct ResampleArgs {
     int num_table;             // table entries per zero crossing (512)
 };
 hipError_t sdfa_launch_resample(const ResampleArgs &a, hipStream_t s);
+// live streams (include/sdfa_stream.h sdfa_stream_resample): input rings -> model rings, all streams of a step in one launch
+constexpr int STREAM_RING_MIRROR = 2048;   // include/sdfa_stream.h SDFA_STREAM_RING_MIRROR
+constexpr int STREAM_MAX_RATES = 8;        // include/sdfa_stream.h SDFA_STREAM_MAX_RATES
+struct StreamRate {
+    const double *win;         // [2 nwin] this rate pair's half filter, then its forward differences
+    int64_t step;              // table entries per input sample; 0: input rate = model rate, the samples are copied
+    double scale;              // min(1, ratio)
+};
+struct StreamResampleArgs {
+    const float *in_rings;     // n_in_rings rings of 2^r_in + STREAM_RING_MIRROR floats
+    float *rings;              // n_rings model rings of 2^r + STREAM_RING_MIRROR floats
+    int r_in, n_in_rings, r, n_rings;
+    const int64_t *seg;        // [n_seg][8], see stream_resample_kernel
+    const double *treg;        // [n_treg] time registers of the outputs, segment by segment
+    int64_t n_treg, nwin;
+    int num_table, n_rates;
+    StreamRate rate[STREAM_MAX_RATES];
+};
+hipError_t sdfa_launch_stream_resample(const StreamResampleArgs &a, int n_seg, int64_t max_count, hipStream_t s);

@@ -8,7 +8,13 @@ still fire then); `close` emits the tail frames past the end of the audio, sdfa_
 
 A step is one host -> device copy (every stream's new samples, the segment table, the frame table and the speaker ids), one
 ring-append launch, the front end (share_prev + the stream kernel + its repair pass), the encoder and the regressor -- whatever
-the number of streams.  The session does not normalise RMS and does not resample: streams arrive at the model rate."""
+the number of streams.
+
+Capture-rate streams (`open(..., input_rate=, gain=)`): the samples go to an input ring, and each step converts the outputs that have
+become final (include/sdfa_stream.h "Capture-rate streams") into the stream's model ring with the offline resampler's arithmetic, a
+float32 gain and the +-0.999 clamp -- one more ring append and one resample launch per step, whatever the number of streams and
+rates.  Such a stream emits the frames of generate_animation(clip(resample(x, input_rate, sr) * gain, -0.999, 0.999)), bit for bit.
+The session does not normalise RMS (a whole-clip statistic: `speech_anime.audio.rms_gain` gives the gain of a known clip)."""
 import ctypes as C
 
 import numpy as np
@@ -20,6 +26,8 @@ from .engine import FEAT_SHAPE, FPS, TS_DELTA_MS, frame_geometry
 ABI_VERSION = 1      # include/sdfa_stream.h SDFA_STREAM_ABI_VERSION this binding was written against
 MAX_SAMPLES = 0x1fffffff
 RING_MIRROR = 2048   # include/sdfa_stream.h SDFA_STREAM_RING_MIRROR
+MAX_RATES = 8        # include/sdfa_stream.h SDFA_STREAM_MAX_RATES
+T_OPEN = (1 << 63) - 1      # t_zero of a resample segment while its stream is open
 
 _p, _i64, _i32 = C.c_void_p, C.c_int64, C.c_int32
 SYMBOLS = {
@@ -28,6 +36,11 @@ SYMBOLS = {
     "sdfa_stream_final_frames": (_i64, [_i64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdfa_stream_ring_append": (C.c_int, [_p, C.c_int, _i32, _p, _i32, _p, _i64, _p]),
     "sdfa_mel_frontend_ring": (C.c_int, [_p, C.c_int, _i32, _p, _p, _i32, _p, _p, _i64, C.c_int, _p, _p, _i64, _p]),
+    "sdfa_stream_resample_final": (_i64, [_i64, C.c_int, C.c_int]),
+    "sdfa_stream_resample_register": (_i64, [_i64, C.c_int, C.c_int, _p, _p]),
+    "sdfa_stream_resample_close": (_i64, [_i64, C.c_int, C.c_int, _p]),
+    "sdfa_stream_resample_wing": (_i64, [C.c_int, C.c_int]),
+    "sdfa_stream_resample": (C.c_int, [_p, C.c_int, _i32, _p, C.c_int, _i32, _p, _i32, _i64, _p, _i64, _p, _i32, C.c_int, _p]),
 }
 
 
@@ -72,17 +85,58 @@ def close_frames(n_samples, sr, fps=FPS):
     return int(check(lib.sdfa_frame_index(int(n_samples), int(sr), int(fps), win, hop, TS_DELTA_MS, None, None, 0)))
 
 
+def resample_final(n_in, input_rate, sr):
+    """Model-rate samples a stream at `input_rate` has made final after n_in input samples (include/sdfa_stream.h)."""
+    return int(check(lib.sdfa_stream_resample_final(int(n_in), int(input_rate), int(sr))))
+
+
+def resample_register(state, count, input_rate, sr):
+    """(time registers float64[count] of `count` consecutive outputs, the carried register after them); `state` is the register of the
+    first (0.0 for output 0).  The sequential accumulation of the offline call, however the calls are cut."""
+    st = C.c_double(float(state))
+    out = np.empty(int(count), np.float64)
+    check(lib.sdfa_stream_resample_register(int(count), int(input_rate), int(sr), C.byref(st), out.ctypes.data_as(C.c_void_p)))
+    return out, st.value
+
+
+def resample_close(n_in, input_rate, sr):
+    """(n_out, n_res) of a stream that ended after n_in input samples: its model-rate length and the outputs that are filtered
+    (zeros behind them).  Raises what the offline `resample` raises ("too small to resample")."""
+    n_res = _i64(0)
+    n_out = int(check(lib.sdfa_stream_resample_close(int(n_in), int(input_rate), int(sr), C.byref(n_res))))
+    return n_out, int(n_res.value)
+
+
+def resample_wing(input_rate, sr):
+    """nwin / step of the rate pair: the reach of one filter wing in input samples (0 for equal rates)."""
+    return int(check(lib.sdfa_stream_resample_wing(int(input_rate), int(sr))))
+
+
+def input_ring_bits(input_rate, sr, budget):
+    """r_in with 2^r_in >= left wing + right wing + push budget (in input samples: `budget` model-rate samples' worth of time) + 1."""
+    wing = resample_wing(input_rate, sr) + 1
+    budget_in = -(-int(budget) * int(input_rate) // int(sr))
+    return max(int(np.ceil(np.log2(2 * wing + budget_in + 1))), 1)
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
 class _Stream:
-    __slots__ = ("sid", "ring", "speaker", "pad", "n_dev", "n_total", "pending", "emitted", "end", "closing", "out_ts", "out_rows")
+    __slots__ = ("sid", "ring", "speaker", "pad", "n_dev", "n_total", "pending", "emitted", "end", "closing", "out_ts", "out_rows",
+                 "rate", "gain", "wing", "in_dev", "in_total", "treg", "n_res")
 
-    def __init__(self, sid, ring, speaker, pad):
+    def __init__(self, sid, ring, speaker, pad, rate=None, gain=1.0):
         self.sid, self.ring, self.speaker, self.pad = sid, ring, speaker, pad
-        self.n_dev = 0              # samples in the ring
-        self.n_total = 0            # ... plus samples pushed and not yet uploaded
+        self.rate, self.gain = rate, gain      # capture-rate stream: its input rate and gain (rate None: samples at the model rate)
+        self.wing = 0               # reach of the left wing in input samples (the sample at n included)
+        self.in_dev = 0             # input samples in the input ring (ring `ring` of the input ring array)
+        self.in_total = 0           # ... plus input samples pushed and not yet uploaded
+        self.treg = 0.0             # time register of output n_dev, the first not yet resampled
+        self.n_res = T_OPEN         # once closed: outputs from here on are zeros
+        self.n_dev = 0              # samples in the ring (capture-rate: outputs resampled so far)
+        self.n_total = 0            # ... plus samples pushed and not yet uploaded (capture-rate: outputs final, or all once closed)
         self.pending = []           # host chunks not yet uploaded
         self.emitted = 0            # frames computed so far
         self.end = None             # frame count once closed
@@ -102,12 +156,15 @@ class LiveSession:
       push_budget       samples a stream may receive between two steps without forcing one (default 1 s)
       max_ensembling_ms the largest `ensembling_ms` an `open` may ask for
       max_step_frames   main frames per launch group (default: the engine's max_frames, halved when a stream ensembles)
+      max_input_rate    the highest `input_rate` an `open` may ask for (sizes the input rings)
 
     Ring size R = 2^r >= sliding + max ensembling pad + push budget + 1.  A push that would overwrite samples that a frame not
-    yet computed still needs runs a step first and keeps its output for the next `step()`, so any chunking works."""
+    yet computed still needs runs a step first and keeps its output for the next `step()`, so any chunking works.  Input ring size
+    R_in = 2^r_in >= both filter wings + the push budget in input samples + 1 at max_input_rate (`input_ring_bits`); the input rings
+    are made by the first step that has a capture-rate stream."""
 
     def __init__(self, engine, max_streams, sample_rate=16000, outputs="rows", host_copy=False, push_budget=None,
-                 max_ensembling_ms=20, max_step_frames=None):
+                 max_ensembling_ms=20, max_step_frames=None, max_input_rate=48000):
         if outputs not in ("rows", "coef"):
             raise ValueError(f"outputs must be 'rows' or 'coef', not {outputs!r}")
         self.eng = engine
@@ -121,6 +178,13 @@ class LiveSession:
         if self.r > 28:
             raise ValueError("ring of more than 2^28 samples: lower push_budget")
         self.R = 1 << self.r
+        self.max_input_rate = int(max_input_rate)
+        self.r_in = input_ring_bits(self.max_input_rate, self.sr, budget)
+        if self.r_in > 28:
+            raise ValueError("input ring of more than 2^28 samples: lower push_budget or max_input_rate")
+        self.R_in = 1 << self.r_in
+        self.in_rings = None
+        self._rates = []            # distinct input rates of the session's streams so far (segments name them by index)
         self.max_streams = int(max_streams)
         self.max_step_frames = int(max_step_frames) if max_step_frames else int(engine.max_frames)
         self.stream = None          # the session's CUDA stream, rings and counters: made by the first step (open / push / close
@@ -147,10 +211,27 @@ class LiveSession:
             self._fe_repairs = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     # ------------------------------------------------------------------ streams
-    def open(self, speaker_id, ensembling_ms=0):
+    def open(self, speaker_id, ensembling_ms=0, input_rate=None, gain=1.0):
         """A new stream for speaker `speaker_id`; its frames average two passes when ensembling_ms > 0 (model.py:373-384).
-        Returns the stream id."""
+        With `input_rate` the stream takes samples at that rate and converts them on the device, times `gain`, clamped to
+        +-0.999 (input_rate = the model rate: gain and clamp alone); without it `gain` must stay 1.  Returns the stream id."""
         self.eng.check_speaker_ids(int(speaker_id))
+        gain = float(gain)
+        f32 = np.finfo(np.float32)
+        if not float(f32.tiny) <= gain <= float(f32.max):          # (NaN fails the comparison too)
+            raise ValueError(f"gain must be finite and > 0, not {gain!r}")
+        if input_rate is None:
+            if gain != 1.0:
+                raise ValueError("gain needs input_rate: a stream at the model rate is taken as it is")
+        else:
+            if int(input_rate) != input_rate or int(input_rate) <= 0:
+                raise ValueError(f"input_rate must be a positive integer, not {input_rate!r}")
+            input_rate = int(input_rate)
+            if input_rate > self.max_input_rate:
+                raise ValueError(f"input_rate={input_rate} is above this session's max_input_rate={self.max_input_rate}")
+            resample_final(0, input_rate, self.sr)                # a rate pair the offline call refuses: its message
+            if input_rate not in self._rates and len(self._rates) >= MAX_RATES:
+                raise ValueError(f"a session takes at most {MAX_RATES} distinct input rates")
         ens = int(ensembling_ms or 0)
         if ens < 0:
             raise ValueError("ensembling_ms must be >= 0")
@@ -163,7 +244,11 @@ class LiveSession:
             raise RuntimeError(f"all {self.max_streams} streams of the session are open")
         sid = self._next_sid
         self._next_sid += 1
-        self._streams[sid] = _Stream(sid, self._free.pop(), int(speaker_id), pad)
+        if input_rate is not None and input_rate not in self._rates:
+            self._rates.append(input_rate)
+        st = self._streams[sid] = _Stream(sid, self._free.pop(), int(speaker_id), pad, input_rate, gain)
+        if input_rate is not None:
+            st.wing = resample_wing(input_rate, self.sr) + 1
         return sid
 
     def _get(self, sid):
@@ -182,7 +267,8 @@ class LiveSession:
         return max(int(s[0]) - st.pad - 1, -st.pad)
 
     def push(self, sid, pcm):
-        """Appends samples (float32 in [-1, 1], at the model rate) to stream `sid`."""
+        """Appends samples (float32 in [-1, 1], at the stream's input rate: the model rate unless it was opened with another) to
+        stream `sid`."""
         st = self._get(sid)
         x = pcm.detach().cpu().numpy() if torch.is_tensor(pcm) else np.asarray(pcm)
         x = np.asarray(x, np.float32).reshape(-1)
@@ -190,6 +276,8 @@ class LiveSession:
             return
         if not (x.min() >= -1 and x.max() <= 1):                 # generate_animation's input check (model.py:339-349)
             raise ValueError("samples must lie in [-1, 1]")
+        if st.rate is not None:
+            return self._push_input(st, x)
         if st.n_total + x.size > MAX_SAMPLES:
             final_frames(st.n_total + x.size, self.sr)            # raises sdfa_frame_index's message
         pos = 0
@@ -207,11 +295,53 @@ class LiveSession:
             st.n_total += take
             pos += take
 
+    def _push_input(self, st, x):
+        """push() of a capture-rate stream.  Two rings bound what fits before a step: the input ring keeps every sample from the left
+        wing of the first output not yet resampled, and the model ring takes the outputs the samples make final."""
+        pos = 0
+        while pos < x.size:
+            oldest = st.n_dev if st.rate == self.sr else int(st.treg) - st.wing   # equal rates: a copy, no wings
+            room = oldest + self.R_in - st.in_total
+            take = min(room, x.size - pos)
+            if take > 0:
+                cap = self._oldest_needed(st) + self.R           # model-rate length the model ring can take before a step
+                n = resample_final(st.in_total + take, st.rate, self.sr)
+                if n > cap:
+                    lo, hi = 0, take                              # the most samples whose final outputs fit (final is monotone)
+                    while hi - lo > 1:
+                        mid = (lo + hi) // 2
+                        if resample_final(st.in_total + mid, st.rate, self.sr) <= cap:
+                            lo = mid
+                        else:
+                            hi = mid
+                    take = lo
+                    n = resample_final(st.in_total + take, st.rate, self.sr)
+            if take <= 0:
+                before = (st.emitted, st.n_dev)
+                self._run_step()
+                if (st.emitted, st.n_dev) == before:
+                    raise RuntimeError("live session: a forced step freed no ring space (rings too small for this stream)")
+                continue
+            if n > MAX_SAMPLES:
+                final_frames(n, self.sr)                          # raises sdfa_frame_index's message
+            st.pending.append(x[pos:pos + take])
+            st.in_total += take
+            st.n_total = n
+            pos += take
+
     def close(self, sid):
         """Ends stream `sid`: the next step emits its tail frames (zero padding past the end, as offline).  A stream shorter than
         one window raises the offline call's short-clip AssertionError and is dropped; other streams are unaffected."""
         st = self._get(sid)
         try:
+            if st.rate is not None:
+                n_out, n_res = resample_close(st.in_total, st.rate, self.sr)      # raises what the offline resample raises
+                if n_out > self._oldest_needed(st) + self.R:
+                    # the outputs held back until now do not fit the model ring: a step computes the final frames and frees it
+                    self._run_step()
+                    if n_out > self._oldest_needed(st) + self.R:
+                        raise RuntimeError("live session: the model ring cannot take the stream's tail (push_budget too small)")
+                st.n_total, st.n_res = n_out, n_res
             st.end = close_frames(st.n_total, self.sr)
         except Exception:
             self._drop(st)
@@ -270,7 +400,26 @@ class LiveSession:
         # streams that ensemble first: their main frames are then one block, averaged with the delayed block in one call
         sts.sort(key=lambda s: (s.pad == 0, s.sid))
         segs, srcs, src_n = [], [], 0
+        in_segs, rs_segs, tregs, treg_n, rs_max = [], [], [], 0, 0
         for st in sts:
+            if st.rate is not None:
+                if st.pending:
+                    cnt = st.in_total - st.in_dev
+                    in_segs.append((st.ring, st.in_dev, cnt, src_n))
+                    srcs.extend(st.pending)
+                    src_n += cnt
+                if st.n_total > st.n_dev:
+                    # outputs n_dev .. n_total - 1, and the zeros at -pad .. -1 ahead of the first of an ensembling stream
+                    lead = st.pad if st.n_dev == 0 else 0
+                    n_reg = max(min(st.n_total, st.n_res) - st.n_dev, 0) if st.rate != self.sr else 0
+                    reg, st.treg = resample_register(st.treg, n_reg, st.rate, self.sr)
+                    rate_gain = self._rates.index(st.rate) | (int(np.float32(st.gain).view(np.uint32)) << 32)
+                    rs_segs.append((st.ring, st.ring, st.n_dev - lead, st.n_total - st.n_dev + lead, st.in_total, st.n_res, treg_n,
+                                    rate_gain - (1 << 64) if rate_gain >= 1 << 63 else rate_gain))
+                    tregs.append(reg)
+                    treg_n += n_reg
+                    rs_max = max(rs_max, st.n_total - st.n_dev + lead)
+                continue
             if st.pending:
                 cnt = st.n_total - st.n_dev
                 lead = st.pad if st.n_dev == 0 else 0      # positions -pad .. -1 of a delayed view read as zeros
@@ -285,9 +434,12 @@ class LiveSession:
             k1 = st.end if st.closing else final_frames(st.n_total, self.sr)
             if k1 > st.emitted:
                 work.append((st, st.emitted, k1))
-        if not segs and not work:
+        if not segs and not in_segs and not rs_segs and not work:
             return
         self._device_init()
+        if in_segs and self.in_rings is None:
+            with torch.cuda.stream(self.stream):
+                self.in_rings = torch.zeros(self.max_streams * (self.R_in + RING_MIRROR), dtype=torch.float32, device=self.device)
         ens_any = any(st.pad > 0 for st, _, _ in work)
         cap = max(1, self.max_step_frames // (2 if ens_any else 1))
         # launch groups of at most `cap` main frames; each holds its streams' main frames, then the delayed ones
@@ -326,11 +478,13 @@ class LiveSession:
                     fspk.append(np.full(k1 - k0, st.speaker, np.int64))
                     d += k1 - k0
             layout.append((m, d))
-        # ONE upload: [segments | view ring | view hi | frame starts | speaker ids] int64, frame views int32, samples float32
+        # ONE upload: [segments | view ring | view hi | frame starts | speaker ids | input-ring segments | resample segments |
+        # time registers (float64)] int64, frame views int32, samples float32
         nseg, nv = len(segs), len(view_ring)
         nf = int(sum(a.size for a in fstart))
         i64 = np.concatenate([np.asarray(segs, np.int64).reshape(-1), np.asarray(view_ring, np.int64), np.asarray(view_hi, np.int64)]
-                             + fstart + fspk)
+                             + fstart + fspk + [np.asarray(in_segs, np.int64).reshape(-1), np.asarray(rs_segs, np.int64).reshape(-1)]
+                             + [t.view(np.int64) for t in tregs])
         fv = np.concatenate(fview) if fview else np.empty(0, np.int32)
         o_fv = i64.size * 8
         o_pcm = (o_fv + fv.size * 4 + 15) // 16 * 16
@@ -348,7 +502,8 @@ class LiveSession:
             for c in srcs:
                 pcm[o:o + c.size] = c
                 o += c.size
-        calls = {"h2d_copy": 1, "ring_append": 0, "frontend_ring": 0, "encoder": 0, "regress": 0, "ensemble_mean": 0, "status_add": 0}
+        calls = {"h2d_copy": 1, "ring_append": 0, "resample": 0, "frontend_ring": 0, "encoder": 0, "regress": 0, "ensemble_mean": 0,
+                 "status_add": 0}
         with torch.cuda.stream(self.stream):
             if self._dev is None or self._dev.numel() < total:
                 self._dev = None
@@ -369,8 +524,22 @@ class LiveSession:
                 check(lib.sdfa_stream_ring_append(_ptr(self.rings), self.r, self.max_streams, C.c_void_p(d_seg), nseg,
                                                   C.c_void_p(base + o_pcm), src_n, sp))
                 calls["ring_append"] += 1
+            if in_segs:
+                d_inseg = d_fspk + nf * 8
+                check(lib.sdfa_stream_ring_append(_ptr(self.in_rings), self.r_in, self.max_streams, C.c_void_p(d_inseg), len(in_segs),
+                                                  C.c_void_p(base + o_pcm), src_n, sp))
+                calls["ring_append"] += 1
+            if rs_segs:
+                d_rsseg = d_fspk + nf * 8 + len(in_segs) * 32
+                rates = (C.c_int32 * len(self._rates))(*self._rates)
+                check(lib.sdfa_stream_resample(_ptr(self.in_rings), self.r_in, self.max_streams, _ptr(self.rings), self.r, self.max_streams,
+                                               C.c_void_p(d_rsseg), len(rs_segs), rs_max, C.c_void_p(d_rsseg + len(rs_segs) * 64), treg_n,
+                                               rates, len(self._rates), self.sr, sp))
+                calls["resample"] += 1
             for st in sts:
-                if st.pending:
+                if st.rate is not None:
+                    st.in_dev, st.n_dev, st.pending = st.in_total, st.n_total, []
+                elif st.pending:
                     st.n_dev = st.n_total
                     st.pending = []
             f0 = 0

@@ -1,6 +1,7 @@
 """Audio ingest helpers on the host (numpy): the steps around the hot path that evaluate() needs.
 
   rms_normalize -- saber.audio.rms.normalize (saber/data/audio/rms.py:45-78), called at speech_anime/model/model.py:165
+  rms_gain      -- the gain rms_normalize applies, for live streams that normalise on the device
   load_source   -- the .wav branch of speech_anime/model/eval_utils.py:50-93
 
 The reference loads everything through librosa at 44.1 kHz and resamples with resampy (kaiser_best); neither library is
@@ -26,6 +27,20 @@ def rms_normalize(wav, target_db=-20, threshold=None):
     rms_db = 20.0 * np.log10(np.sqrt(np.mean(wav[keep] ** 2)))
     gain = np.power(10.0, (target_db - rms_db) / 20.0)
     return np.clip(wav * gain, -0.999, 0.999)
+
+
+def rms_gain(wav, target_db=-20, threshold=None):
+    """The np.float32 gain `rms_normalize` applies to a float32 signal (1 where it returns its input untouched):
+    np.clip(wav * rms_gain(wav, target_db), -0.999, 0.999) == rms_normalize(wav, target_db) exactly for float32 `wav`, the product
+    of a float32 array and numpy's float64 scalar being a float32 multiply by the rounded scalar.  What a live stream takes as its
+    `gain` (sdfa_amd.live): RMS normalisation needs the whole clip, so the caller supplies it."""
+    wav = np.asarray(wav)
+    level = 20.0 * np.log10(np.maximum(np.abs(wav), 1e-10))
+    keep = level >= (level.min() if threshold is None else threshold)
+    if not keep.any():
+        return np.float32(1.0)
+    rms_db = 20.0 * np.log10(np.sqrt(np.mean(wav[keep] ** 2)))
+    return np.float32(np.power(10.0, (target_db - rms_db) / 20.0))
 
 
 SOUND_SR = 44100      # every source is first brought to 44.1 kHz (eval_utils.py:77,83; also the rate of the exported audio.wav)

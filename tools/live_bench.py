@@ -1,9 +1,10 @@
 """Live streaming throughput (sdfa_amd/live.py): S streams each push 1/60 s of synthetic speech-like audio per tick, then one
 step() runs every stream's new frames.  Per (rate, S, output mode): wall time of the pushes and of the step (the step timed to the
 device's completion), p50 / p99 over the measured ticks, and whether a 60 ticks/s cadence fits.  Synthetic dgrad weights (the
-timing does not depend on the values).
+timing does not depend on the values).  With --input-rate the streams are capture-rate streams: each pushes 1/60 s of audio at that
+rate per tick and the step resamples it on the device (default output profiles/live_resample_bench.json).
 
-  python tools/live_bench.py --out profiles/live_bench.json [--ticks 60] [--streams 1,64,256,1024,2048]"""
+  python tools/live_bench.py --out profiles/live_bench.json [--ticks 60] [--streams 1,64,256,1024,2048] [--input-rate 44100]"""
 import argparse
 import json
 import os
@@ -22,13 +23,17 @@ from sdfa_amd.engine import Engine, frame_geometry    # noqa: E402
 TICK_MS = 1000.0 / 60
 
 
-def run(eng, sr, S, mode, ticks, pcm):
+def run(eng, sr, S, mode, ticks, pcm, input_rate=None):
     outputs, host = {"rows": ("rows", False), "rows+host": ("rows", True), "coef+host": ("coef", True)}[mode]
-    s = live.LiveSession(eng, S, sample_rate=sr, outputs=outputs, host_copy=host, max_step_frames=eng.max_frames)
-    sids = [s.open(i % 8) for i in range(S)]
-    per_tick = sr // 60
+    if input_rate is None:
+        s = live.LiveSession(eng, S, sample_rate=sr, outputs=outputs, host_copy=host, max_step_frames=eng.max_frames)
+        sids = [s.open(i % 8) for i in range(S)]
+    else:
+        s = live.LiveSession(eng, S, sample_rate=sr, outputs=outputs, host_copy=host, max_step_frames=eng.max_frames, max_input_rate=input_rate)
+        sids = [s.open(i % 8, input_rate=input_rate, gain=0.9) for i in range(S)]
+    per_tick = (input_rate or sr) // 60
     _, _, sliding = frame_geometry(sr)
-    warm = sliding // per_tick + 3                        # until every stream emits a frame per tick
+    warm = sliding // (sr // 60) + (3 if input_rate is None else 5)      # until every stream emits a frame per tick
     pos, push_ms, step_ms, frames = 0, [], [], []
     for t in range(warm + ticks):
         t0 = time.perf_counter()
@@ -51,7 +56,8 @@ def run(eng, sr, S, mode, ticks, pcm):
     s.step()
     p = lambda a, q: float(np.percentile(a, q))
     tot = [a + b for a, b in zip(push_ms, step_ms)]
-    return {"sr": sr, "streams": S, "mode": mode, "ticks": ticks, "frames_per_tick_mean": float(np.mean(frames)),
+    extra = {} if input_rate is None else {"input_rate": input_rate, "input_ring_samples": s.R_in}
+    return {**extra, "sr": sr, "streams": S, "mode": mode, "ticks": ticks, "frames_per_tick_mean": float(np.mean(frames)),
             "step_ms_p50": p(step_ms, 50), "step_ms_p99": p(step_ms, 99), "push_ms_p50": p(push_ms, 50), "push_ms_p99": p(push_ms, 99),
             "tick_ms_p99": p(tot, 99), "sustains_60_ticks_per_s": p(tot, 99) <= TICK_MS, "calls_per_step": calls, "health": h,
             "ring_samples": s.R}
@@ -59,24 +65,28 @@ def run(eng, sr, S, mode, ticks, pcm):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "live_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--input-rate", type=int, default=None, help="capture rate of every stream (default: streams at the model rate)")
+    ap.add_argument("--modes", default="rows,rows+host,coef+host")
     ap.add_argument("--ticks", type=int, default=60)
     ap.add_argument("--streams", default="1,64,256,1024,2048,4096")
     ap.add_argument("--rates", default="8000,16000")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "live_bench.json" if a.input_rate is None else "live_resample_bench.json")
     results = []
     sd = synth.make_state_dict("dgrad", 1234)
     for sr in [int(x) for x in a.rates.split(",")]:
         eng = Engine(sd, device="cuda:0", max_frames=8192)
-        pcm = synth.make_pcm(5, 20 * sr)
+        pcm = synth.make_pcm(5, 20 * (a.input_rate or sr))
         best = 0
         for S in [int(x) for x in a.streams.split(",")]:
             row = None
-            for mode in ("rows", "rows+host", "coef+host"):
-                row = run(eng, sr, S, mode, a.ticks, pcm)
+            for mode in a.modes.split(","):
+                row = run(eng, sr, S, mode, a.ticks, pcm, a.input_rate)
                 results.append(row)
                 print(json.dumps(row), flush=True)
-            ok = [r for r in results if r["sr"] == sr and r["streams"] == S and r["mode"] == "rows"][0]["sustains_60_ticks_per_s"]
+            ok = [r for r in results if r["sr"] == sr and r["streams"] == S and r["mode"] == a.modes.split(",")[0]][0]["sustains_60_ticks_per_s"]
             if ok:
                 best = S
             else:
