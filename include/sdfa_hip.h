@@ -298,6 +298,10 @@ int sdfa_ensemble_mean(const float *d_a, const float *d_b, int64_t n, float *d_o
  *                      over 2 cooperating workgroups that exchange h every step -- 16-frame tiles on v_mfma_f32_16x16x4_f32 up to 1,024
  *                      frames (time_lstm_split16_kernel), 32-frame tiles up to 2,048 (time_lstm_split_kernel); 1 = never; 32 = 32-frame
  *                      tiles only; 16 = 16-frame tiles or an error
+ *   "time_lstm_fuse_x" layer 1 of the BiLSTM (exact fp32, no debug taps) as ONE kernel that contracts [x_t | h] against the concatenated
+ *                      weights every step (time_lstm_fused_kernel) instead of the input-projection GEMM + time_lstm_kernel: 0 = where the
+ *                      launch would be one workgroup per tile (not the small-batch cooperating forms) and the last round of that grid
+ *                      fills at least 93 % of the CUs, 1 = never, 2 / 3 = always, with 32- / 64-frame tiles.  Same bits
  *   "time_lstm_handoff" how those workgroups publish / consume h: 0 = write-through (sc1) stores + sc1 loads (default); bit 0 = plain
  *                      stores + agent-scope release; bit 1 = agent-scope acquire + plain loads (the always-valid form, slower);
  *                      bit 2 (tests only) = the second workgroup of every pair never publishes, so every wait of the first expires

@@ -42,6 +42,7 @@ thread_local int g_sdfa_pca_lds = 0;
 thread_local int g_sdfa_pca_fp32 = 0;     // "pca_fp32": 1 = the dgrad PCA expansion stays on the fp32 kernel in SDFA_PREC_BF16X3 (A/B)
 thread_local int g_sdfa_conv_fp32 = 0;    // "conv_fp32": 1 = the conv stack stays on the fp32 kernel in the mixed-precision modes (A/B)
 thread_local int g_sdfa_time_lstm_split = 0;
+thread_local int g_sdfa_time_lstm_fuse_x = 0;   // "time_lstm_fuse_x": layer 1 of the BiLSTM contracts its input projection inside the recurrence: 0 = by size, 1 = never, 2 / 3 = always (32- / 64-frame tiles)
 thread_local int g_sdfa_time_lstm_handoff = 0;
 thread_local int g_sdfa_time_lstm_timeout_us = 0;
 thread_local int g_sdfa_share_gx0_off = 0;
@@ -76,6 +77,7 @@ int sdfa_debug_set_option(const char *name, int value) {
         {"time_lstm_timeout_us", &g_sdfa_time_lstm_timeout_us},
         {"time_lstm_handoff", &g_sdfa_time_lstm_handoff},
         {"time_lstm_split", &g_sdfa_time_lstm_split},
+        {"time_lstm_fuse_x", &g_sdfa_time_lstm_fuse_x, 0, 3, "0 (rule), 1 (never), 2 or 3 (always, 32- / 64-frame tiles)"},
         {"gemm_variant", &g_sdfa_gemm_variant},
         {"freq_lstm_shape", &g_sdfa_freq_lstm_shape},
         {"pca_lds", &g_sdfa_pca_lds},

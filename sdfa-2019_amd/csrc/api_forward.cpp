@@ -277,10 +277,16 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
             gi.terms = stage_terms(m, STAGE_BODY);
             gi.reserve_cus = m->reserved_cus.load();
             if (mapped) gi.q_limit = d_ulimit;
-            pf.begin(gxn[l]); HIP_TRY(sdfa_launch_gemm(gi, s)); pf.end();
             TimeLstmArgs ta{gx, m->tl_w[l], hout[l], Nc, Mc, m->tl_wb[l], stage_terms(m, STAGE_BODY),
                             reinterpret_cast<unsigned *>(ws + w.CT_FLAG), CT_WORDS - CT_FLAGS, m->tl_w16[l],
                             reinterpret_cast<unsigned *>(ws), m->reserved_cus.load(), mapped ? col_to_u : nullptr};
+            // Layer 1, exact fp32, large chunks: the recurrence contracts [x_t | h] itself (time_lstm_fused_kernel), so the projection GEMM and
+            // the round trip of its 2048 x Mc output through HBM go away; the GX region stays unused.  (The debug taps keep the two-kernel
+            // path.)  The stage name stays, empty, for the profile readers; "lstm1" then carries the fused kernel's time.
+            if (l == 1 && !m->keep) { ta.X = xin; ta.Wxh = m->tl_wxh1; }
+            pf.begin(gxn[l]);
+            if (!sdfa_time_lstm_fuses_x(ta)) HIP_TRY(sdfa_launch_gemm(gi, s));
+            pf.end();
             pf.begin(lsn[l]); HIP_TRY(sdfa_launch_time_lstm(ta, s)); pf.end();
             xin = hout[l];
         }

@@ -354,6 +354,19 @@ int sdfa_model_finalize(sdfa_model *m, void *stream) {
                 else if (o != first + (size_t)64 * 1024 * 4) return sdfa_fail(SDFA_ESTATE, "internal: time-lstm weights not contiguous");
             }
             pk.bind(m->gx_w[l], pack_k4(pk, both.data(), 2048, Kin, Kin, 0, Kin, 2048));
+            if (l == 1) {
+                // the fused recurrence (time_lstm_fused_kernel) contracts [x_t | h] itself: per direction ONE image, K4 [128 k-quads of
+                // W_ih | 64 of W_hh][1024 packed gate rows][4], so its K loop walks the two parts without a break
+                const size_t o_x = pk.bind(m->tl_wxh1, pk.add((size_t)2 * 192 * 1024 * 4));
+                for (int d = 0; d < 2; ++d) {
+                    auto *whh = get(m, enc + "9.weight_hh_l1" + suf[d], (size_t)1024 * 256);
+                    float *img = &pk.buf[o_x + (size_t)d * 192 * 1024 * 4];
+                    for (int p = 0; p < 1024; ++p) {
+                        for (int k = 0; k < 512; ++k) img[((size_t)(k / 4) * 1024 + p) * 4 + k % 4] = both[((size_t)d * 1024 + p) * 512 + k];
+                        for (int k = 0; k < 256; ++k) img[((size_t)(128 + k / 4) * 1024 + p) * 4 + k % 4] = (*whh)[(size_t)perm[p] * 256 + k];
+                    }
+                }
+            }
         }
     }
     // ---- attention

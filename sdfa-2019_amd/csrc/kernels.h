@@ -151,8 +151,12 @@ struct TimeLstmArgs {
     unsigned *status;    // word 0 of the workspace's status block: counts the waits of the small-batch form that expired (null = not counted)
     int reserve_cus;     // the small-batch form is used while its grid fits (CUs - reserve_cus)
     const int32_t *col_map;   // column sharing, layer 0: GX holds the DISTINCT columns; column (t, n) reads GX column col_map[t * Nc + n] (null = its own)
+    const float *X = nullptr;    // time_lstm_fused_kernel (layer 1): the layer's input, K4 [512/4][Mc]; null = the projection comes from GX
+    const float *Wxh = nullptr;  // time_lstm_fused_kernel: per direction K4 [(512+256)/4][1024][4], W_ih then W_hh (api_model.cpp); null = not packed
 };
 hipError_t sdfa_launch_time_lstm(const TimeLstmArgs &a, hipStream_t s);
+// 0 = the launch reads its input projection from GX (the caller runs the projection GEMM first); 1 / 2 = it contracts X itself, 32- / 64-frame tiles
+int sdfa_time_lstm_fuses_x(const TimeLstmArgs &a);
 
 // ---- attention scores / softmax / context ---------------------------------------------------
 struct AttnArgs {

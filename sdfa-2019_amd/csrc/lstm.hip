@@ -1221,6 +1221,182 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
 template <int NT, bool MAP = false>
 __global__ __launch_bounds__(512, 2) void time_lstm_kernel(TimeLstmArgs a) { time_lstm_body<NT, MAP>(a); }
 
+// ------------------------------------------------------------------------- time LSTM, input projection fused (layer 1)
+// time_lstm_kernel with the input projection contracted INSIDE the recurrence, as the frequency LSTM does: every step contracts
+// [x_t | h_{t-1}] (K = 512 + 256) against the concatenated weight image a.Wxh, so the 2048 x Mc projections never go to HBM and no
+// step waits for its seeds.  Same workgroup shape, cell function and H stores as time_lstm_body; bit-identical to GEMM + time_lstm_kernel:
+// an accumulator starts from zero, takes the x products in the GEMM's order (ascending k-block, q = 0..3: gemm.hip) and then the h
+// products as before -- the GEMM's fp32 store / reload in between changed no bit.
+//   * LDS (float4 rows of BT columns): [h parity 0: 64 rows | h parity 1: 64 rows | x buffer 0: 16 rows | x buffer 1: 16 rows], 160 KiB
+//     for NT = 2.  One K-loop trip = 8 k-blocks = 16 rows, so a trip's operand rows are one base pointer + immediates whatever they hold.
+//   * the x part is 8 trips over 8 slices of 16 k-quad rows of X[:, t * Nc + n0 ..]; trip i requests the NEXT slice of the sequence (the
+//     last trip of a step: slice 0 of the next step, which does not depend on h_t) with plain 16-byte loads behind the weight requests
+//     of its first k-block -- loads return in issue order, so no weight wait includes the slice's HBM round trip -- writes it to the
+//     other buffer three k-blocks later and hands it over with one workgroup barrier in its last k-block.  (LDS-DMA is not used: the
+//     compiler puts a full vmcnt(0) in front of every LDS read that follows a request, and the K loop reads LDS every k-block.)
+//   * the step's first MFMA group takes a literal zero as its C operand: no zero fill.
+template <int NT>
+__global__ __launch_bounds__(512, 2) void time_lstm_fused_kernel(TimeLstmArgs a) {
+    extern __shared__ float4 sHt[];   // [2][64][BT] h | [2][16][BT] x
+    constexpr int BT = 32 * NT;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;   // 8 waves: hidden block of 32
+    const int l31 = lane & 31, h = lane >> 5;
+    const int dir = blockIdx.x & 1;
+    const int64_t n0 = (int64_t)(blockIdx.x >> 1) * BT;
+
+    float4 *__restrict__ H = reinterpret_cast<float4 *>(a.H);
+    float4 *const sX = sHt + 2 * 64 * BT;
+
+    f32x16 c[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c[j][r] = 0.f;
+
+    // x slices: wave w stages rows 2w, 2w + 1 of a slice -- NT 2: one 64-column row per load, NT 1: both rows' 32 columns in one load
+    const float4 *__restrict__ Xl = reinterpret_cast<const float4 *>(a.X) + (int64_t)(2 * wave + (NT == 1 ? h : 0)) * a.Mc + n0 + (NT == 1 ? l31 : lane);
+    float4 *const xw = sX + 2 * wave * BT + lane;        // this lane's slot in x buffer 0 (NT 2: + 64 for the second row)
+    float4 xr0, xr1;      // (named scalars: as an array the pair lived in scratch memory)
+#define TF_XLOAD(t_, sl)                                                                                         \
+    {                                                                                                            \
+        const float4 *xs = Xl + (int64_t)((sl) * 16) * a.Mc + (int64_t)(t_) * a.Nc;                              \
+        xr0 = xs[0];                                                                                             \
+        if (NT > 1) xr1 = xs[a.Mc];                                                                              \
+    }
+#define TF_XSTORE(buf)                                                                                           \
+    {                                                                                                            \
+        xw[(buf) * 16 * BT] = xr0;                                                                               \
+        if (NT > 1) xw[(buf) * 16 * BT + 64] = xr1;                                                              \
+    }
+    float4 *__restrict__ Hl = H + (int64_t)(dir * 64 + wave * 8 + h) * a.Mc + n0 + l31;
+
+    // weights: one image per direction, [128 k-quads of W_ih | 64 of W_hh][1024 gate rows][4], through a buffer descriptor one
+    // k-block ahead (see time_lstm_body); the request that wraps around at the end of a step is k-block 0 of the next step
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const unsigned long long wptr = (unsigned long long)(reinterpret_cast<const float4 *>(a.Wxh) + (size_t)dir * 192 * 1024 + wave * 128);
+    const unsigned long long wuni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wptr >> 32)) << 32) |
+                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wptr);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wuni, 0, (192 * 1024 - 7 * 128) * 16, 0x00020000);
+    const unsigned woff = (unsigned)((l31 + h * 1024) * 16);
+#define TF_W1(so, g_) __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + 512 * (g_), so, 0))
+    constexpr unsigned KB = 2048 * 16;      // bytes of one k-block of the image
+    float4 wn0, wn1, wn2, wn3;
+    TF_XLOAD(dir ? 63 : 0, 0)
+    wn0 = TF_W1(0u, 0); wn1 = TF_W1(0u, 1); wn2 = TF_W1(0u, 2); wn3 = TF_W1(0u, 3);
+    TF_XSTORE(0)
+    __syncthreads();
+
+#define TF_SB() __builtin_amdgcn_sched_barrier(0);
+#define TF_Q(W0, W1, W2, W3, B, q)                                                                               \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[0][j] = MFMA(f4c(W0, q), f4c(B[j], q), acc[0][j]);        \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[1][j] = MFMA(f4c(W1, q), f4c(B[j], q), acc[1][j]);        \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[2][j] = MFMA(f4c(W2, q), f4c(B[j], q), acc[2][j]);        \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[3][j] = MFMA(f4c(W3, q), f4c(B[j], q), acc[3][j]);
+    // the step's first MFMA group: C = 0
+#define TF_QZ(W0, W1, W2, W3, B, q)                                                                              \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[0][j] = MFMA(f4c(W0, q), f4c(B[j], q), zero16);           \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[1][j] = MFMA(f4c(W1, q), f4c(B[j], q), zero16);           \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[2][j] = MFMA(f4c(W2, q), f4c(B[j], q), zero16);           \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[3][j] = MFMA(f4c(W3, q), f4c(B[j], q), zero16);
+    // one k-block on the operand set C* while the set N* is refilled for the next one (time_lstm_body's TL_KB); Q0 = its first
+    // MFMA group, AFTER_W = what rides behind its weight requests, AT_B = what rides with its first operand read
+#define TF_KB_(Q0, AFTER_W, AT_B, CW0, CW1, CW2, CW3, CB, NW0, NW1, NW2, NW3, NB, so, bp)                        \
+    {                                                                                                            \
+        TF_SB() NW0 = TF_W1(so, 0); NW1 = TF_W1(so, 1); TF_SB()                                                  \
+        Q0(CW0, CW1, CW2, CW3, CB, 0)                                                                            \
+        TF_SB() NW2 = TF_W1(so, 2); NW3 = TF_W1(so, 3); AFTER_W TF_SB()                                          \
+        TF_Q(CW0, CW1, CW2, CW3, CB, 1)                                                                          \
+        TF_SB() AT_B NB[0] = (bp)[0]; TF_SB()                                                                    \
+        TF_Q(CW0, CW1, CW2, CW3, CB, 2)                                                                          \
+        TF_SB() if (NT > 1) NB[NT - 1] = (bp)[32 * (NT - 1)]; TF_SB()                                            \
+        TF_Q(CW0, CW1, CW2, CW3, CB, 3)                                                                          \
+    }
+#define TF_NONE
+#define TF_KB(...) TF_KB_(TF_Q, TF_NONE, TF_NONE, __VA_ARGS__)
+    // every wave's slice writes (and its reads of the buffer they replace, one trip back) are done: hand the buffer over
+#define TF_HANDOVER asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // a trip of the x part: 8 k-blocks on x buffer (i & 1); the next slice is requested in k-block 0, written in k-block 3 and handed
+    // over in k-block 7, in front of the first read of it (the operands of the next trip's k-block 0)
+#define TF_XTRIP(Q0, i_)                                                                                                          \
+    {                                                                                                                             \
+        const int nb = ((i_) & 1) ^ 1;                                                                                            \
+        const float4 *bt = xrow + ((i_) & 1) * 16 * BT;                                                                           \
+        const float4 *bn = (i_) < 7 ? xrow + nb * 16 * BT : hrow;                                                                 \
+        const unsigned so = (unsigned)(i_) * (8 * KB);                                                                            \
+        const unsigned son = ((i_) < 7 || s > 0) ? so + 8 * KB : 0u;     /* step 0 has no h part: k-block 0 of the next step */   \
+        const int tl = (i_) < 7 ? t : tn, sl = (i_) < 7 ? (i_) + 1 : 0;                                                           \
+        TF_KB_(Q0, TF_XLOAD(tl, sl), TF_NONE, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 1 * KB, bt + 1 * 2 * BT)      \
+        TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 2 * KB, bt + 2 * 2 * BT)                                       \
+        TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 3 * KB, bt + 3 * 2 * BT)                                       \
+        TF_KB_(TF_Q, TF_NONE, TF_XSTORE(nb), wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 4 * KB, bt + 4 * 2 * BT)        \
+        TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 5 * KB, bt + 5 * 2 * BT)                                       \
+        TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 6 * KB, bt + 6 * 2 * BT)                                       \
+        TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 7 * KB, bt + 7 * 2 * BT)                                       \
+        TF_KB_(TF_Q, TF_NONE, TF_HANDOVER, wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, son, bn)                               \
+    }
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float4 *const xrow = sX + h * BT + l31;         // row pair of k-block kb of an x trip: xrow + buffer * 16 * BT + kb * 2 * BT
+    for (int s = 0; s < 64; ++s) {
+        const int t = dir ? 63 - s : s;
+        const int tn = s + 1 < 64 ? (dir ? t - 1 : t + 1) : t;      // behind the last step: this step's slice again (never used)
+        const int64_t tcol = (int64_t)t * a.Nc;
+        const float4 *hrow = sHt + (size_t)(s & 1) * 64 * BT + h * BT + l31;
+        float4 *sHn = sHt + (size_t)((s & 1) ^ 1) * 64 * BT;
+
+        f32x16 acc[4][NT];
+        float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba[NT], bb[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) ba[j] = xrow[j * 32];
+        // trip 0 is written out in front of the loop: its first MFMA group is the zero-seeded one (a run-time test inside the loop
+        // would make the compiler copy accumulators around the branch: freq_lstm_v3_kernel)
+        TF_XTRIP(TF_QZ, 0)
+#pragma unroll 1
+        for (int i = 1; i < 8; ++i) TF_XTRIP(TF_Q, i)
+        if (s > 0) {      // h_{-1} = 0: the first step contracts x only
+#pragma unroll 1
+            for (int tr = 0; tr < 4; ++tr) {
+                const float4 *bt = hrow + tr * 16 * BT;
+                const float4 *bn = tr + 1 < 4 ? bt + 16 * BT : xrow;        // behind the last trip: dropped ...
+                const unsigned so = (unsigned)(8 + tr) * (8 * KB);
+                const unsigned son = tr + 1 < 4 ? so + 8 * KB : 0u;         // ... whose weights ARE k-block 0 of the next step
+                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 1 * KB, bt + 1 * 2 * BT)
+                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 2 * KB, bt + 2 * 2 * BT)
+                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 3 * KB, bt + 3 * 2 * BT)
+                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 4 * KB, bt + 4 * 2 * BT)
+                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 5 * KB, bt + 5 * 2 * BT)
+                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 6 * KB, bt + 6 * 2 * BT)
+                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 7 * KB, bt + 7 * 2 * BT)
+                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, son, bn)
+            }
+        }
+        TF_SB()
+        wn0 = wa0; wn1 = wa1; wn2 = wa2; wn3 = wa3;      // k-block 0 again: the next step's first operands
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float4 hq;
+                lstm_cell_quad(acc[0][j], acc[1][j], acc[2][j], acc[3][j], c[j], g, hq);
+                const int hq_idx = 8 * wave + 2 * g + h;
+                sHn[hq_idx * BT + j * 32 + l31] = hq;
+                Hl[(int64_t)(2 * g) * a.Mc + tcol + j * 32] = hq;
+            }
+        __syncthreads();   // h_s complete in sHn before anyone reads it; the other parity free for step s+1's writes
+    }
+#undef TF_XTRIP
+#undef TF_HANDOVER
+#undef TF_KB
+#undef TF_NONE
+#undef TF_KB_
+#undef TF_QZ
+#undef TF_Q
+#undef TF_SB
+#undef TF_W1
+#undef TF_XSTORE
+#undef TF_XLOAD
+}
+
 // The same recurrence as a REPAIR pass behind a launch of the cooperating-workgroup kernels below: every workgroup reads that launch's
 // time-out word and exits at once unless a workgroup of it gave up waiting for its partner -- in which case this pass, which needs no
 // co-residency and cannot time out, recomputes the layer's H rows from the (untouched) input projections.  So a time-out costs time,
@@ -1991,28 +2167,52 @@ static hipError_t launch_time_split16(const TimeLstmArgs &a, hipStream_t s) {
 }
 
 extern thread_local int g_sdfa_time_lstm_split;   // api.cpp ("time_lstm_split" option): 0 = by size, 1 = never
+extern thread_local int g_sdfa_time_lstm_fuse_x;  // api.cpp ("time_lstm_fuse_x" option): 0 = by rule, 1 = never, 2 / 3 = always, 32- / 64-frame tiles
+
+// 64-frame tiles while they fill the 256 CUs (one 8-wave workgroup per CU); otherwise 32-frame tiles
+static bool time_big(const TimeLstmArgs &a) { return (a.Nc / 64) * 2 >= 256; }
+
+// Which small-batch form a launch takes: 0 = none (one workgroup per tile), 2 = time_lstm_split_kernel<2>, 16 = time_lstm_split16_kernel,
+// -1 = 16-frame tiles asked for and not possible at this size
+static int time_split_form(const TimeLstmArgs &a) {
+    if (a.terms || !a.flags || g_sdfa_time_lstm_split == 1) return 0;
+    // small batches: the gate rows of a tile split over G cooperating workgroups (time_lstm_split_kernel).  They exchange h
+    // every step, so all of them should be resident at once: only while the grid fits the CUs this model may use (one
+    // workgroup per CU; sdfa_model_set_reserved_cus leaves some to other streams)
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    cus -= a.reserve_cus;
+    const int64_t wg1 = a.Nc / 32 * 2;                       // workgroups of time_lstm_kernel<1>
+    const bool range_ok = (int64_t)64 * a.Mc * 16 + (int64_t)a.Mc * 16 < 0x7fffffff && a.Nc % 128 == 0 && a.flag_words >= wg1 * 2 + 4;   // buffer offsets; 8-block groups
+    // 16-frame tiles (time_lstm_split16_kernel) while even their grid -- twice the workgroups -- fits the CUs; option 16 / 32 force one
+    if (range_ok && a.W16 && g_sdfa_time_lstm_split != 32 && wg1 * 4 <= cus && a.flag_words >= wg1 * 4 + 4) return 16;
+    if (g_sdfa_time_lstm_split == 16) return -1;      // asked for, not possible at this size
+    // G = 2: four waves per workgroup, one per SIMD.  (G = 4 -- two waves per workgroup -- was measured too: no faster, a wave's
+    // matrix work per step is the same; profiles/r03_time_lstm_split.txt.)
+    return (range_ok && wg1 * 2 <= cus) ? 2 : 0;
+}
+
+template <int NT>
+static hipError_t launch_time_fused(const TimeLstmArgs &a, hipStream_t s) {
+    if (a.Nc % (32 * NT)) return hipErrorInvalidValue;
+    const size_t lds = (2 * 64 + 2 * 16) * 32 * NT * sizeof(float4);   // 160 KiB (NT 2) / 80 KiB (NT 1)
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(time_lstm_fused_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((time_lstm_fused_kernel<NT>), dim3((unsigned)(a.Nc / (32 * NT) * 2)), dim3(512), lds, s, a);
+    return hipGetLastError();
+}
 
 template <bool MAP>
 static hipError_t launch_time_any(const TimeLstmArgs &a, hipStream_t s) {
-    // 64-frame tiles while they fill the 256 CUs (one 8-wave workgroup per CU); otherwise 32-frame tiles
-    const bool big = (a.Nc / 64) * 2 >= 256;
-    if (!a.terms && a.flags && g_sdfa_time_lstm_split != 1) {
-        // small batches: the gate rows of a tile split over G cooperating workgroups (time_lstm_split_kernel).  They exchange h
-        // every step, so all of them should be resident at once: only while the grid fits the CUs this model may use (one
-        // workgroup per CU; sdfa_model_set_reserved_cus leaves some to other streams)
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        cus -= a.reserve_cus;
-        const int64_t wg1 = a.Nc / 32 * 2;                       // workgroups of time_lstm_kernel<1>
-        const bool range_ok = (int64_t)64 * a.Mc * 16 + (int64_t)a.Mc * 16 < 0x7fffffff && a.Nc % 128 == 0 && a.flag_words >= wg1 * 2 + 4;   // buffer offsets; 8-block groups
-        // G = 2: four waves per workgroup, one per SIMD.  (G = 4 -- two waves per workgroup -- was measured too: no faster, a wave's
-        // matrix work per step is the same; profiles/r03_time_lstm_split.txt.)
-        const int G = (range_ok && wg1 * 2 <= cus) ? 2 : 0;
-        // 16-frame tiles (time_lstm_split16_kernel) while even their grid -- twice the workgroups -- fits the CUs; option 16 / 32 force one
-        if (range_ok && a.W16 && g_sdfa_time_lstm_split != 32 && wg1 * 4 <= cus && a.flag_words >= wg1 * 4 + 4) return launch_time_split16<MAP>(a, s);
-        if (g_sdfa_time_lstm_split == 16) return hipErrorInvalidValue;      // asked for, not possible at this size
-        if (G == 2) return launch_time_split<2, MAP>(a, s);
+    const bool big = time_big(a);
+    if (!MAP) {
+        const int nt = sdfa_time_lstm_fuses_x(a);
+        if (nt) return nt == 2 ? launch_time_fused<2>(a, s) : launch_time_fused<1>(a, s);
     }
+    const int split = time_split_form(a);
+    if (split == 16) return launch_time_split16<MAP>(a, s);
+    if (split < 0) return hipErrorInvalidValue;
+    if (split == 2) return launch_time_split<2, MAP>(a, s);
     if (a.terms) {
         if (!a.Wb || MAP) return hipErrorInvalidValue;      // the bf16 recurrences read un-shared input projections (api.cpp expands first)
         if (a.terms == 6) return launch_time_bf16<1, 6>(a, s);      // three planes of h: 32-frame tiles only (96 KiB of LDS)
@@ -2020,6 +2220,24 @@ static hipError_t launch_time_any(const TimeLstmArgs &a, hipStream_t s) {
         return big ? launch_time_bf16<2, 3>(a, s) : launch_time_bf16<1, 3>(a, s);
     }
     return big ? launch_time<2, MAP>(a, s) : launch_time<1, MAP>(a, s);
+}
+
+// Whether (and with how many 32-frame column tiles per workgroup) a launch contracts its input projection inside the recurrence
+// (time_lstm_fused_kernel) instead of reading it from a.GX: the caller then skips the projection GEMM.  Only where the launch would
+// otherwise be one workgroup per tile of the exact fp32 kernel and fills the chip: the small-batch forms and the bf16 modes keep the two-kernel path.
+int sdfa_time_lstm_fuses_x(const TimeLstmArgs &a) {
+    if (!a.X || !a.Wxh || a.terms || a.col_map || g_sdfa_time_lstm_fuse_x == 1) return 0;
+    if (g_sdfa_time_lstm_fuse_x == 2) return 1;
+    if (g_sdfa_time_lstm_fuse_x == 3) return 2;
+    if (time_split_form(a) != 0) return 0;
+    // The fused kernel puts the projection's matrix work (two thirds of the layer's) on the CUs its grid reaches, where the GEMM used the whole
+    // chip: it pays while the grid's last round of one workgroup per CU is nearly full.  From the per-launch times of an 8,192- and a
+    // 3,968-frame chunk (profiles/lstm1_fused_ab.txt: 10.91 against 7.53 + 4.10 ms, 5.52 against 3.67 + 2.03) the break-even is a last round
+    // 90 - 92 % full; 93 % here.
+    const int nt = time_big(a) ? 2 : 1;
+    const int64_t wgs = a.Nc / (32 * nt) * 2, cus = std::max(1, sdfa_cu_count());
+    const int64_t rounds = (wgs + cus - 1) / cus;
+    return wgs * 100 >= rounds * cus * 93 ? nt : 0;
 }
 
 hipError_t sdfa_launch_time_lstm(const TimeLstmArgs &a, hipStream_t s) {

@@ -25,6 +25,7 @@ struct sdfa_model {
     const float *gx_w[2], *tl_w[2];
     const void *tl_wb[2] = {nullptr, nullptr};   // BiLSTM recurrent weights as bf16 hi/lo planes (mixed-precision modes)
     const float *tl_w16[2] = {nullptr, nullptr}; // BiLSTM recurrent weights in the operand order of time_lstm_split16_kernel
+    const float *tl_wxh1 = nullptr;              // layer 1 of the BiLSTM: [W_ih | W_hh] along K per direction, the operand image of time_lstm_fused_kernel
     const float *kp_w, *qc_w, *qp_w, *at_v, *at_b;
     struct Fc { const float *w, *b, *cw; int K, P, Ppad, Pstore; int act; };
     Fc trunk, br[2][3], off[3];
