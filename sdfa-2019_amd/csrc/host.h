@@ -1,4 +1,4 @@
-// Host-side helpers shared by the api_*.cpp files and the host parts of render.hip / jpeg.hip: the error path and round_up.
+// Host-side helpers shared by the api_*.cpp files and the host parts of render.hip / jpeg.hip / obj.hip: the error path and round_up.
 #pragma once
 #include "../../include/sdfa_hip.h"
 

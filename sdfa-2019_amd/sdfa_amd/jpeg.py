@@ -8,6 +8,7 @@ import ctypes as C
 import torch
 
 from ._lib import lib, check, SdfaError
+from ._packed import PackedReadback, ptr as _ptr, stream as _stream
 from .render import CHUNK_FRAMES
 
 ABI_VERSION = 1      # include/sdfa_jpeg.h SDFA_JPEG_ABI_VERSION this binding was written against
@@ -43,30 +44,12 @@ def _bind():
 _bind()
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-class PendingChunk:
+class PendingChunk(PackedReadback):
     """One encode call in flight: the file lengths are on their way to pinned host memory; result() waits for them, then
     reads back exactly the encoded bytes in one copy and splits them into files."""
 
-    def __init__(self, out, meta_dev, meta_host, event, n):
-        self._out, self._meta_dev, self._meta_host, self._event, self._n = out, meta_dev, meta_host, event, n
-
     def result(self):
-        if self._n == 0:
-            return []
-        self._event.synchronize()
-        meta = self._meta_host.numpy()
-        offs, lens = meta[:self._n], meta[self._n:]
-        total = int(offs[-1] + lens[-1])
-        data = self._out[:total].cpu().numpy().tobytes()
-        return [data[o:o + ln] for o, ln in zip(offs.tolist(), lens.tolist())]
+        return self.records()
 
 
 class JpegEncoder:
@@ -120,17 +103,13 @@ class JpegEncoder:
         n = rgb.shape[0]
         assert n <= self.chunk, (n, self.chunk)
         if n == 0:
-            return PendingChunk(None, None, None, None, 0)
+            return PendingChunk(None, None, 0)
         out = torch.empty(n * self.max_frame_bytes, dtype=torch.uint8, device=self.device)
         meta = torch.empty(2 * n, dtype=torch.int64, device=self.device)          # offsets, then lengths
         ws = self._workspace(n)
         check(lib.sdfa_jpeg_encode(self._e, _ptr(rgb), n, _ptr(out), out.numel(), _ptr(meta), C.c_void_p(meta.data_ptr() + 8 * n),
                                    _ptr(ws), ws.numel(), _stream()))
-        host = torch.empty(2 * n, dtype=torch.int64, pin_memory=True)
-        host.copy_(meta, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return PendingChunk(out, meta, host, ev, n)
+        return PendingChunk(out, meta, n)
 
     def encode(self, rgb):
         """(n, H, W, 3) (or (H, W, 3)) uint8 cuda frames -> list of n JPEG files (bytes)."""

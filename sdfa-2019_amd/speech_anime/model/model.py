@@ -392,18 +392,16 @@ class SaberSpeechDrivenAnimation:
             plan = SeekPlan([tslist], fps, device=eng.device)
             if track is None:                                       # the group took several pieces: re-upload this clip's rows (model.py:200)
                 track = torch.from_numpy(np.ascontiguousarray(animes, dtype=np.float32)).to(eng.device).reshape(len(tslist), -1)
-            frames = plan.rows(track).cpu().numpy().reshape((plan.n_queries,) + animes.shape[1:])
+            rows = plan.rows(track)
+            frames = rows.cpu().numpy().reshape((plan.n_queries,) + animes.shape[1:])
             for i_frame, data_frame in enumerate(frames):
                 np.save(os.path.join(out_dir, f"{i_frame:06d}_dgrad.npy"), data_frame)
-            if viewer.has_template():          # --template_mesh given: seek + solve on the GPU, then .obj per frame
-                if self._face_type == "dgrad_3d":
-                    verts, faces = viewer.track_to_mesh(track, plan).cpu().numpy(), viewer.template_faces()
-                elif viewer.has_source_mesh():     # offsets head retargeted on the device: deform_grad + the template's solve
-                    verts, faces = viewer._device_verts(plan.rows(track), self._face_type).cpu().numpy(), viewer.template_faces()
-                else:
-                    verts, faces = viewer.frames_to_mesh(frames.astype(np.float32), self._face_type)
-                for i_frame in range(len(frames)):
-                    viewer.write_obj(os.path.join(out_dir, f"{i_frame:06d}.obj"), verts[i_frame], faces)
+            if viewer.has_template():          # --template_mesh given: seek + solve on the GPU, then .obj per frame, its text
+                if self._face_type == "dgrad_3d":                                       # formatted there too (sdfa_amd.obj)
+                    verts = viewer.track_to_mesh(track, plan)
+                else:     # offsets head: with a source mesh retargeted on the device (deform_grad + the template's solve), else + template
+                    verts = viewer._device_verts(rows, self._face_type)
+                viewer.write_obj_frames(out_dir, verts, viewer.template_faces())
         if video_size is not None:
             video_path = os.path.join(output_dir, name + ".avi")        # model.py:197-203: export_dir = splitext(video_path)[0]
             self._write_video(video_path, g, tslist, animes, track, video_size, jpeg_encoder)

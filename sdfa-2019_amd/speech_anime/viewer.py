@@ -2,6 +2,8 @@
 dgrad / offsets frame into vertices, backed by the GPU deformation solve (sdfa_amd.mesh), including retargeting to a
 template of another topology through triangle correspondences (--mesh_tricorres) -- and the rendering of those vertices into
 images on the GPU (render_frame / render_track, sdfa_amd.render; viewer/render_py.py in the reference)."""
+import os
+
 import numpy as np
 import torch
 
@@ -12,6 +14,7 @@ _template_c_indices = []
 _template_corres = None
 _solver = None
 _renderers = {}          # (image_size, samples, normals) -> sdfa_amd.render.Renderer of the current template, made on first use
+_obj_writers = {}        # device -> sdfa_amd.obj.ObjWriter of the current template (its face block formatted once), made on first use
 
 
 def read_obj(path):
@@ -37,6 +40,30 @@ def write_obj(path, verts, faces):
             fp.write("f {} {} {}\n".format(*(f + 1)))
 
 
+def obj_writer(device):
+    """The .obj writer of the current template on `device` (sdfa_amd.obj.ObjWriter), created on first use."""
+    assert _solver is not None, "set_template_mesh first"
+    device = torch.device(device)
+    if device not in _obj_writers:
+        from sdfa_amd.obj import ObjWriter
+        _obj_writers[device] = ObjWriter(_template_faces, len(_template_verts), device=device)
+    return _obj_writers[device]
+
+
+def write_obj_frames(out_dir, verts, faces):
+    """<out_dir>/NNNNNN.obj for every frame of the (n, V, 3) float32 cuda vertices, each file what write_obj writes for it: the
+    numbers are formatted on the device (sdfa_amd.obj), the face block once per template.  `faces` other than the current
+    template's get a writer of their own."""
+    assert torch.is_tensor(verts) and verts.is_cuda and verts.dim() == 3, "write_obj_frames takes (n, V, 3) cuda vertices"
+    if faces is _template_faces and verts.shape[1] == len(_template_verts):
+        writer = obj_writer(verts.device)
+    else:
+        from sdfa_amd.obj import ObjWriter
+        writer = ObjWriter(faces, verts.shape[1], device=verts.device)
+    writer.write([os.path.join(out_dir, f"{i:06d}.obj") for i in range(verts.shape[0])], verts)
+    return writer
+
+
 N_MODEL_TRIS = 9976      # triangles of the model's FLAME-topology dgrad rows (frame.py:117: 89784 = 9976 * 9)
 N_MODEL_VERTS = 5023     # vertices of the model's FLAME-topology offsets rows (15069 = 5023 * 3)
 
@@ -53,6 +80,7 @@ def set_dgrad_static(verts, faces, c_indices=None, corres=None):
     fewer vertices than those indices address fails here like the reference's native module does on them."""
     global _template_verts, _template_faces, _template_c_indices, _template_corres, _solver
     _renderers.clear()                   # a renderer is prepared lazily for the new template (renderer())
+    _obj_writers.clear()                 # and so is the .obj writer (write_obj_frames)
     _template_verts = np.asarray(verts, np.float32).reshape(-1, 3)
     _template_faces = np.asarray(faces, np.uint32).reshape(-1, 3)
     if c_indices is None:
@@ -109,6 +137,7 @@ def clear_template():
     _template_verts = _template_faces = _template_corres = _solver = None
     _template_c_indices = []
     _renderers.clear()
+    _obj_writers.clear()
 
 
 def template_faces():
