@@ -25,16 +25,19 @@ class SeekPlan:
     """For a batch of clips: which two animation-frame rows each video frame blends, and with which float32 weights.
 
     tslists: per clip, the ascending integer millisecond timestamps of its animation frames (sdfa_frame_index);
-    the rows of the matrix to be resampled are the clips' frames concatenated in this order."""
+    the rows of the matrix to be resampled are the clips' frames concatenated in this order.
+    query_counts: per clip, how many uniform queries to plan instead of model.py's count (stream.seek itself takes any time:
+    queries past a clip's last timestamp copy its last row)."""
 
-    def __init__(self, tslists, fps, device="cuda:0"):
+    def __init__(self, tslists, fps, device="cuda:0", query_counts=None):
         if not torch.cuda.is_available():
             raise RuntimeError("sdfa_amd.seek needs a ROCm GPU: there is no CPU implementation")
         self.device = torch.device(device)
         self.fps = float(fps)
         counts = [len(t) for t in tslists]
         assert all(c > 0 for c in counts), "every clip needs at least one animation frame"
-        self.query_counts = [query_count(t[-1], fps) for t in tslists]
+        self.query_counts = [query_count(t[-1], fps) for t in tslists] if query_counts is None else [int(q) for q in query_counts]
+        assert len(self.query_counts) == len(counts) and all(q >= 0 for q in self.query_counts)
         self.frame_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.query_off = np.concatenate([[0], np.cumsum(self.query_counts)]).astype(np.int64)
         self.n_frames, self.n_queries = int(self.frame_off[-1]), int(self.query_off[-1])
