@@ -1,8 +1,8 @@
 """SpeechDrivenAnimation / SaberSpeechDrivenAnimation -- inference surface of speech_anime/model/model.py.
 
 Same method names, arguments and result layouts as the reference; the arithmetic is libsdfa_hip.so.
-Not mirrored (out of scope): training (train_step/get_loss), TensorBoard hooks, titles and the multi-source
-grid of the evaluate video.  evaluate() writes the dgrad track, .obj files with a template mesh and, with save_video, an
+Not mirrored (out of scope): training (train_step, get_loss as a training objective), TensorBoard hooks, titles and
+the multi-source grid of the evaluate video.  get_loss's validation scalars are validate() (sdfa_amd.score).  evaluate() writes the dgrad track, .obj files with a template mesh and, with save_video, an
 .avi rendered on the GPU (sdfa_amd.render, speech_anime.video).
 """
 import os
@@ -277,6 +277,78 @@ class SaberSpeechDrivenAnimation:
         others = {"inputs": inputs_host.numpy() if inputs_host is not None else None,
                   "phones": None, "latent": None, "latent_align": None, "formants": None}
         return animes, others
+
+    # ---- model.py:261-330 (get_loss's scalars on held-out tracks) ---------------------------------
+    @torch.no_grad()
+    def validate(self, clips, frames="inference", anime_loss_weight=None, keep_rows=False):
+        """The reference's validation scalars (get_loss with PLoss / MLoss, criterion.py) of this checkpoint on held-out clips:
+        {"clips": [per clip: scalar_ps, scalar_pr, scalar_ms, scalar_mr, scalar_ploss, scalar_mloss, frames], "corpus": the same keys,
+        the mean over clips weighted by their frame counts}.  The offsets head carries its whole loss in scalar_ps / scalar_ms
+        (= scalar_ploss / scalar_mloss; pr = mr = 0).
+
+        clips: each (signal, speaker, track, start_ts, anime_minfi, anime_maxfi) or a dict with those keys (`minfi`, `maxfi`;
+        optionally `lips_dist`): track = the float32 rows of track frames anime_minfi .. anime_maxfi, or a directory of NNNNNN.npy.
+        frames: "inference" scores the frames generate_animation produces (sdfa_frame_index); "dataset" the windows the
+        reference's dataset enumerates (sliding_window.py:45-61), without its random shift.  One pass, no ensembling, as the
+        reference validates.  anime_loss_weight="anime_weight" weights the frames by exp((0.002 - lips_dist) * 50) * 2.
+        The rows stay on the device; sdfa_amd.score reads each prediction element once.
+        Absent: ELoss (no evector here) and DynamicLossScaler (its state is not in a checkpoint)."""
+        from sdfa_amd import score
+        from sdfa_amd.engine import frame_index, frame_geometry
+        from .. import validate as _v
+        eng = self._model._engine
+        if eng is None:
+            raise RuntimeError("no weights loaded: call load_state_dict first")
+        if frames not in ("inference", "dataset"):
+            raise ValueError(f"frames must be 'inference' or 'dataset', got {frames!r}")
+        if anime_loss_weight not in (None, "anime_weight"):
+            raise ValueError(f"anime_loss_weight must be None or 'anime_weight', got {anime_loss_weight!r}")
+        sr, fps, ts_delta = self.hp.audio.sample_rate, self.hp.anime.fps, self.hp.anime.feature.ts_delta
+        sliding = frame_geometry(sr)[2]
+        signals, speakers, tables, tracks, plans, weights, base = [], [], [], [], [], [], 0
+        for ci, clip in enumerate(clips):
+            c = clip if isinstance(clip, dict) else dict(zip(("signal", "speaker", "track", "start_ts", "minfi", "maxfi"), clip))
+            signal = self._check_signal(c["signal"])
+            spk = self._speakers_dict[c["speaker"]] if isinstance(c["speaker"], str) else c["speaker"]
+            eng.check_speaker_ids(int(spk))
+            minfi, maxfi = int(c["minfi"]), int(c["maxfi"])
+            track = _v.load_track(c["track"], minfi, maxfi) if isinstance(c["track"], (str, os.PathLike)) else c["track"]
+            track = (track if torch.is_tensor(track) else torch.from_numpy(np.asarray(track, np.float32))).reshape(maxfi - minfi + 1, -1)
+            if frames == "inference":
+                starts, ts = frame_index(len(signal), sr, fps, ts_delta)
+            else:
+                starts = score.dataset_frame_starts(len(signal), sr, fps, sliding)
+                ts = np.zeros(len(starts), np.int32)
+            if len(starts) < 2:
+                raise ValueError(f"clip {ci}: {len(starts)} frame, the motion loss needs at least 2")
+            src, w = score.truth_plan(starts, sr, float(c["start_ts"]), minfi, maxfi, fps, ts_delta, sliding)
+            if anime_loss_weight is not None:
+                if c.get("lips_dist") is None:
+                    raise ValueError(f"clip {ci}: anime_loss_weight needs the track's lips_dist values")
+                weights.append(score.anime_weights(c["lips_dist"], src - minfi, w))
+            plans.append((src - minfi + base, w))
+            base += track.shape[0]
+            signals.append(signal); speakers.append(int(spk)); tables.append((starts, ts)); tracks.append(track)
+        feat, _, counts = eng.mel_frontend(signals, sr, tables=tables)
+        fclip, fstart, hop = eng.last_frame_table
+        n = int(sum(counts))
+        spk = torch.from_numpy(np.repeat(np.asarray(speakers, np.int64), counts)).to(eng.device)
+        rows = torch.empty((n, eng.out_dim), dtype=torch.float32, device=eng.device)
+        for f0 in range(0, n, eng.max_frames):                           # the batch path's launch groups; the rows never leave the device
+            f1 = min(n, f0 + eng.max_frames)
+            z, _ = eng.encoder(feat[f0:f1], want_align=False, frame_clip=fclip[f0:f1], frame_start=fstart[f0:f1], hop=hop)
+            eng.regress(z, spk[f0:f1], out=rows[f0:f1], check_ids=False)
+        d_track = torch.cat([t.to(device=eng.device, dtype=torch.float32) for t in tracks])
+        assert d_track.shape[1] == eng.out_dim, f"track rows of {d_track.shape[1]} values, the head writes {eng.out_dim}"
+        off = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        dgrad = self._face_type == "dgrad_3d"
+        rec = score.score_rows(rows, d_track, np.concatenate([p[0] for p in plans]), np.concatenate([p[1] for p in plans]), off,
+                               score.LAYOUT_DGRAD if dgrad else score.LAYOUT_PLAIN)
+        res = score.clip_scalars(rec, off, eng.out_dim // 9 if dgrad else eng.out_dim, np.concatenate(weights) if weights else None)
+        if keep_rows:
+            res.update(rows=rows, records=rec, plan=(np.concatenate([p[0] for p in plans]), np.concatenate([p[1] for p in plans])), track=d_track,
+                       clip_frame_off=off)
+        return res
 
     # ---- model.py:121-223 (host loop: dgrad track dump, mesh export, video rendered on the GPU) ----
     def evaluate(self, sources, experiment=None, in_trainer=False, **kwargs):
