@@ -28,6 +28,9 @@ def _parser():
     # not a reference flag: the FLAME neutral .obj the offsets head's rows are measured from; with it the offsets head is retargeted to
     # --template_mesh (any topology, through --mesh_tricorres) by the deformation transfer the dgrad head uses
     ap.add_argument("--source_mesh", type=str, default=None)
+    # not a reference flag: a temporal filter of the animation rows, applied on the GPU where the reference's identity hook _filter_anime
+    # sits: gaussian:SIGMA or bilateral:DISTANCE_SIGMA,RANGE_SIGMA,RADIUS[,FACTOR] (sdfa_amd.tfilter.parse_filter)
+    ap.add_argument("--filter_anime", type=str, default=None, metavar="SPEC")
     return ap
 
 

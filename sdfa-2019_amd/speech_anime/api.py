@@ -49,6 +49,9 @@ def evaluate_model(args):
             raise ValueError("--source_mesh needs --template_mesh <obj>: the offsets are retargeted onto that template")
         from . import viewer
         viewer.set_source_mesh(args["source_mesh"])                     # refuses a non-FLAME source before any device work
+    if args.get("filter_anime"):                                        # not a reference flag: a bad spec is refused here
+        from sdfa_amd.tfilter import parse_filter
+        parse_filter(args["filter_anime"])
     hparams = configure(args)
     if hparams.eval_input is not None:                                  # api.py:83-87
         rec = [hparams.eval_input]
@@ -76,7 +79,7 @@ def evaluate_model(args):
                           overwrite_video=args.get("overwrite_video", False),
                           export_mesh_frames=args.get("export_mesh_frames", False), keep_results=not from_cli,
                           save_video=args.get("save_video", False), grid_w=args.get("grid_w") or 512, grid_h=args.get("grid_h") or 512,
-                          jpeg_encoder=args.get("jpeg_encoder") or "pil",
+                          jpeg_encoder=args.get("jpeg_encoder") or "pil", filter_anime=args.get("filter_anime"),
                           with_title=args.get("with_title", False), draw_truth=args.get("draw_truth", False),
                           draw_align=args.get("draw_align", False), draw_latent=args.get("draw_latent", False),
                           output_dir=args.get("output_dir") or os.path.join(hparams.get("log_dir") or ".", "evaluate_videos"))

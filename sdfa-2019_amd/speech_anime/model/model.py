@@ -141,8 +141,15 @@ class SaberSpeechDrivenAnimation:
         The default dataset class takes the device pipeline of `generate_animation_batch` (one front-end call, column-sharing
         encoder, ensembling mean on the device, one pinned device -> host copy); a caller-supplied `dataset_class` keeps the
         reference's two-step route through its `fetch_audio_features` and `_feature_to_anime`.  `animes` is a view of pinned host
-        memory owned by the returned array.  kwargs: want_inputs (default True, as the reference returns others["inputs"])."""
+        memory owned by the returned array.  kwargs: want_inputs (default True, as the reference returns others["inputs"]);
+        filter_anime (default None): a sdfa_amd.tfilter.parse_filter spec, "gaussian:SIGMA" or
+        "bilateral:DISTANCE_SIGMA,RANGE_SIGMA,RADIUS[,FACTOR]" -- the rows are filtered along time on the device where the
+        reference's identity hook _filter_anime sits (model.py:405-406,420), after the ensembling mean."""
         signal = self._check_signal(signal)
+        filter_anime = kwargs.get("filter_anime")
+        if filter_anime is not None:
+            from sdfa_amd.tfilter import parse_filter
+            filter_anime = parse_filter(filter_anime)                   # a bad spec is refused before any device work
         if dataset_class is None:
             dataset_class = DatasetSlidingWindow
         if isinstance(speaker, str):
@@ -152,7 +159,7 @@ class SaberSpeechDrivenAnimation:
         if ensembling_ms is None:
             ensembling_ms = self.hp.ensembling_ms
         if dataset_class is DatasetSlidingWindow:
-            return self._animate([signal], [speaker], ensembling_ms, kwargs.get("want_inputs", True))[0]
+            return self._animate([signal], [speaker], ensembling_ms, kwargs.get("want_inputs", True), filter_anime)[0]
 
         passes = [signal]
         if ensembling_ms is not None and ensembling_ms > 0:            # model.py:373-384: second pass on a delayed copy
@@ -165,21 +172,28 @@ class SaberSpeechDrivenAnimation:
             anime_sum += self._feature_to_anime(f["audio_feat"], f["energy"], speaker, emotion, frame_id, want_inputs=False)[0]
         if len(feats) > 1:
             anime_sum = anime_sum / float(len(feats))
+        if filter_anime is not None:
+            flat = torch.from_numpy(np.ascontiguousarray(anime_sum, np.float32)).reshape(len(anime_sum), -1)
+            anime_sum = self._filter_rows(flat, [len(flat)], filter_anime).numpy().reshape(anime_sum.shape)
         return feats[0]["tslist"], anime_sum, others
 
     @torch.no_grad()
-    def generate_animation_batch(self, signals, speakers, emotions=0, frame_id=0, ensembling_ms=None, want_inputs=False):
+    def generate_animation_batch(self, signals, speakers, emotions=0, frame_id=0, ensembling_ms=None, want_inputs=False, filter_anime=None):
         """Several utterances through ONE launch group: [(tslist, animes, others)] in the order of `signals`, each exactly
         what `generate_animation` returns for that clip alone (frames are independent and a column's features do not depend
-        on the batch, so the rows are bitwise the single-clip rows).  `speakers`: one name / id, or one per clip."""
+        on the batch, so the rows are bitwise the single-clip rows).  `speakers`: one name / id, or one per clip.
+        `filter_anime`: as in generate_animation; every clip is filtered on its own, never across a clip boundary."""
         signals = [self._check_signal(s) for s in signals]
+        if filter_anime is not None:
+            from sdfa_amd.tfilter import parse_filter
+            filter_anime = parse_filter(filter_anime)
         if isinstance(speakers, (str, int, np.integer)):
             speakers = [speakers] * len(signals)
         assert len(speakers) == len(signals)
         speakers = [self._speakers_dict[s] if isinstance(s, str) else s for s in speakers]
         if ensembling_ms is None:
             ensembling_ms = self.hp.ensembling_ms
-        return self._animate(signals, speakers, ensembling_ms, want_inputs)
+        return self._animate(signals, speakers, ensembling_ms, want_inputs, filter_anime)
 
     def animation_stream(self, speaker, emotion=0, frame_id=0, ensembling_ms=None, input_rate=None, gain=1.0):
         """generate_animation for audio that arrives in pieces: an object whose push(chunk) and finish() each return
@@ -197,7 +211,21 @@ class SaberSpeechDrivenAnimation:
             ensembling_ms = self.hp.ensembling_ms
         return AnimationStream(self, int(speaker), int(ensembling_ms or 0), input_rate, gain)
 
-    def _animate(self, signals, speakers, ensembling_ms, want_inputs):
+    def _filter_rows(self, rows, counts, spec, device_rows=None):
+        """The filter_anime hook: the pinned host rows of consecutive clips (`counts` frames each) are filtered along time on the
+        device, clip by clip, and written back in place.  `device_rows`: their device copy when it is still there, else they are
+        uploaded.  evaluate (self._keep_filtered) also keeps the filtered device rows, for its exports.  Returns rows."""
+        from sdfa_amd import tfilter
+        eng = self._model._engine
+        n = int(sum(counts))
+        off = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        src = device_rows if device_rows is not None else rows[:n].to(eng.device)
+        filtered = tfilter.apply(spec, src.reshape(n, -1), clip_frame_off=off)
+        rows[:n].copy_(filtered)
+        self._filtered_rows = filtered if getattr(self, "_keep_filtered", False) else None
+        return rows
+
+    def _animate(self, signals, speakers, ensembling_ms, want_inputs, filter_anime=None):
         from sdfa_amd.engine import frame_index
         eng = self._model._engine
         if eng is None:
@@ -223,6 +251,8 @@ class SaberSpeechDrivenAnimation:
             spk = torch.full((n,), int(speakers[0]), dtype=torch.int64, device=eng.device)
             inputs_host = eng.to_host_async(c["feat"][:n].permute(0, 3, 2, 1)) if want_inputs else None
             rows = eng.forward_host(None, spk, z=c["z"], ops_key=self._model._key, wait=True, ensemble=ensemble)
+            if filter_anime is not None:
+                self._filter_rows(rows, [n], filter_anime, eng.last_device_rows(n))
             return [self._pack(rows.numpy(), None if inputs_host is None else inputs_host.numpy(), [list(c["tslist"])], [n])[0]]
         self._signal_cache = None
         tables = [frame_index(len(s), sr) for s in signals]             # ONE enumeration per clip (starts, tslist)
@@ -244,6 +274,8 @@ class SaberSpeechDrivenAnimation:
             # z is 2 KB per frame; the features (others["inputs"] of a later hit) are 98 KB per frame and are kept up to 256 MB only
             keep_feat = feat if feat.numel() * 4 <= (256 << 20) else None
             self._signal_cache = {"key": key, "signal": signals[0].copy(), "tslist": list(tslists[0]), "z": eng.last_z(), "feat": keep_feat}
+        if filter_anime is not None:
+            self._filter_rows(rows, counts, filter_anime, eng.last_device_rows(n))
         return self._pack(rows.numpy(), inputs_host.numpy() if inputs_host is not None else None, tslists, counts)
 
     def _pack(self, rows_np, inputs_np, tslists, counts):
@@ -361,7 +393,13 @@ class SaberSpeechDrivenAnimation:
         kwargs["save_video"] (the reference's --save_video): also write <output_dir>/<name>.avi, grid_w x grid_h, rendered on the GPU
         from the template mesh (speech_anime.video); it needs a template (--template_mesh) and fails before any device work without
         one.  Titles and the truth / latent / alignment panels of the reference's grid are not drawn.  kwargs["jpeg_encoder"]: "pil"
-        (default, host threads) or "gpu" (sdfa_amd.jpeg) encodes the video's frames; both write the same bytes."""
+        (default, host threads) or "gpu" (sdfa_amd.jpeg) encodes the video's frames; both write the same bytes.
+        kwargs["filter_anime"]: a temporal filter spec as in generate_animation; everything returned, written, exported or rendered
+        is the filtered track."""
+        filter_anime = kwargs.get("filter_anime")
+        if filter_anime is not None:
+            from sdfa_amd.tfilter import parse_filter
+            filter_anime = parse_filter(filter_anime)
         save_video = bool(kwargs.get("save_video", False))
         jpeg_encoder = kwargs.get("jpeg_encoder") or "pil"
         from .. import video as _video
@@ -400,9 +438,14 @@ class SaberSpeechDrivenAnimation:
             nonlocal group, group_frames
             if not group:
                 return
-            outs = self.generate_animation_batch([g["signal"] for g in group], [g["spk"] for g in group], ensembling_ms=ens, want_inputs=False)
+            if filter_anime is not None:
+                self._keep_filtered = export_frames or save_video
+            outs = self.generate_animation_batch([g["signal"] for g in group], [g["spk"] for g in group], ensembling_ms=ens, want_inputs=False,
+                                                 filter_anime=filter_anime)
             total = sum(len(o[0]) for o in outs)
             track_all = eng.last_device_rows(total) if (export_frames or save_video) else None      # one piece: the rows are still on the device
+            if filter_anime is not None and track_all is not None:
+                track_all = self._filtered_rows                        # the staging buffer holds the unfiltered rows
             f0 = 0
             for g, (tslist, animes, _) in zip(group, outs):
                 track = None if track_all is None else track_all[f0:f0 + len(tslist)]
@@ -411,6 +454,8 @@ class SaberSpeechDrivenAnimation:
                                    jpeg_encoder)
                 if keep:
                     results.append((g["path"], tslist, animes))
+            if filter_anime is not None:
+                self._keep_filtered, self._filtered_rows = False, None
             group, group_frames = [], 0
 
         # Utterance-level shards (north_star): with kwargs["shard"] = (rank, world) rank r takes a contiguous block of the
