@@ -12,9 +12,9 @@ Pinned to the reference project's fixtures by tests/test_stage_ref64_cpu.py.
 Both output heads: `head="dgrad"` (scale / rotation regressors, two PCA inversions interleaved) and `head="offsets"` (three FCs to
 59 coefficients, one PCA inversion to 15,069 columns).
 
-The keyword arguments `drop_h`, `stale` and `drop_mean` perturb the reference the way a subtle kernel bug would (a step that
-loses its recurrent input, a work unit that reads the wrong time step, an output column without its mean term); the GPU tests
-use them to show that their bounds catch such a bug.
+The keyword arguments `drop_h`, `stale`, `drop_mean` and `bf16_basis` perturb the reference the way a subtle kernel bug would (a
+step that loses its recurrent input, a work unit that reads the wrong time step, an output column without its mean term, a PCA
+expansion whose basis keeps its bf16 high term only); the GPU tests use them to show that their bounds catch such a bug.
 """
 import numpy as np
 import torch
@@ -152,16 +152,19 @@ class StageRef64:
         return torch.cat([cs, cr], -1)
 
     @torch.no_grad()
-    def expand(self, coef, drop_mean=None):
+    def expand(self, coef, drop_mean=None, bf16_basis=False):
         """dgrad: coef (n, 265) -> rows (n, 89784): both PCA inversions, interleaved per triangle as (6 scale, 3 rotation) values;
-        offsets: coef (n, 59) -> rows (n, 15069), one PCA inversion.  drop_mean: a column of the rows whose mean term is left out."""
+        offsets: coef (n, 59) -> rows (n, 15069), one PCA inversion.  drop_mean: a column of the rows whose mean term is left out.
+        bf16_basis: the basis rounded to bf16 (its high term alone: what a split-bf16 expansion computes once it loses the low terms
+        of the basis); the means and the coefficients stay as they are."""
         coef = self._in(coef)
         n = coef.shape[0]
+        basis = (lambda b: b.bfloat16().double()) if bf16_basis else (lambda b: b)
         if self.head == "offsets":
-            rows = coef @ self.pca[0].T + self.pca[1]
+            rows = coef @ basis(self.pca[0]).T + self.pca[1]
         else:
-            s = (coef[:, :85] @ self.pca_s[0].T + self.pca_s[1]).reshape(n, -1, 6)
-            r = (coef[:, 85:] @ self.pca_r[0].T + self.pca_r[1]).reshape(n, -1, 3)
+            s = (coef[:, :85] @ basis(self.pca_s[0]).T + self.pca_s[1]).reshape(n, -1, 6)
+            r = (coef[:, 85:] @ basis(self.pca_r[0]).T + self.pca_r[1]).reshape(n, -1, 3)
             rows = torch.cat([s, r], -1).reshape(n, -1)
         if drop_mean is not None:
             rows[:, drop_mean] -= self.row_means()[drop_mean]

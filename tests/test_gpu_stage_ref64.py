@@ -13,8 +13,11 @@ Bounds are on max|gpu - ref| / max|ref| of a stage, over every frame of every si
 tile, a unit boundary, the padded tail) or to one step of a recurrence shows at that scale; the sensitivity controls at the
 bottom show that it does.
 
-The debug_keep engine swaps the fused conv stack and the share-map recurrence for their unfused forms; every size here is also
-run through the shipping engine, which must give the same bits.
+The debug_keep engine swaps the fused conv stack and the share-map recurrence for their unfused forms, and keeps layer 1 of the
+BiLSTM on the projection GEMM + time_lstm_kernel pair: the shipping engine's layer 1 contracts its input projection inside the
+recurrence (time_lstm_fused_kernel<1> / <2>, lstm.hip sdfa_time_lstm_fuses_x) wherever one workgroup per tile fills the last round
+of the CUs to 93 % -- at 8,192 frames among others -- so the float64 comparison of the taps never runs that kernel itself.  Every
+size here is also run through the shipping engine, which must give the same bits; that comparison is what covers it.
 
 The offsets head (three FCs to 59 coefficients, the PCA expansion to 15,069 columns) is checked at the same sizes by the section at
 the bottom: its coefficients and rows against float64, the ragged last column tile, rows written through a 4-byte-aligned output
@@ -76,6 +79,74 @@ def attention_form(nc, cus):
     while ts < 3 and ((nc // 16) << ts) < 2 * cus:
         ts += 1
     return f"attn_key_score_f32_kernel+attn_kernel<true> ts_shift={ts}"
+
+
+# The launch choices of the mixed-precision modes (tests/test_gpu_stage_mixed_ref64.py), restated from the launch code.
+# api_forward.cpp stage_terms: bf16 terms per operand of the (body, attention, regressor) contractions; 0 = that stage's fp32 kernels.
+MIXED_TERMS = {"bf16x3": (3, 3, 3), "bf16x6": (6, 6, 6), "bf16x3_attention": (0, 3, 0), "bf16": (1, 1, 1)}
+PCA_TRIANGLE_BLOCKS = 312      # pca.hip: (29,928 rotation columns + 95) / 96
+
+
+def split_gemm_form(terms, ppad, qpad, cus):
+    """gemm.hip launch_any with GemmArgs.terms set: the 256 x 256 tile where it divides the problem and gives at least half the
+    CUs a tile, else the 128 x 128 one.  (K is a multiple of 16 in every GEMM of the model, as the six-product big tile asks.)"""
+    big = ppad % 256 == 0 and qpad % 256 == 0 and (ppad // 256) * (qpad // 256) * 2 >= cus
+    if terms == 6:
+        return "gemm_bf16x6_big_kernel" if big else "gemm_bf16x6_kernel"
+    return f"gemm_bf16_big_kernel<{terms}>" if big else f"gemm_bf16_kernel<{terms}>"
+
+
+def key_score_ts_shift(nc, cus):
+    """attn.hip sdfa_launch_attn_key_score: a work unit is 16 frames x (64 >> ts_shift) time steps."""
+    ts = 0
+    while ts < 3 and ((nc // 16) << ts) < 2 * cus:
+        ts += 1
+    return ts
+
+
+def mixed_forms(mode, nc, cus):
+    """stage -> the kernels a chunk of nc frames launches for it in a mixed-precision mode of the dgrad model; only the stages
+    that run kernels of the mode's own (an fp32 stage of such a mode is the arithmetic test_stage_against_float64 covers).
+      conv3    conv123_bf16_kernel at every size (conv.hip)
+      freq     lstm.hip launch_freq_bf16: one persistent workgroup per CU pulling 2 nc 64-column tiles from a queue -- one round of
+               the queue, or several -- then the Linear(8192 -> 256) as a split GEMM over Mc = 64 nc columns
+      bilstm   the input projections (2048 x Mc) as split GEMMs; lstm.hip launch_time_any / time_big: 64-frame tiles from
+               (nc / 64) * 2 >= 256 workgroups on, except in the six-product mode (three planes of h: 32-frame tiles only)
+      z        the query Conv1d (512 x nc) and projection (128 x nc) as split GEMMs, then attn_key_score_kernel<terms> +
+               attn_kernel<true> at the ts_shift of the size; sdfa_attn_fuses_tail never applies at 1 or 3 terms.  The six-product
+               mode runs the fp32 key-score / one-launch kernels behind its query GEMMs.
+      coef     the regressor's FCs (512, 256 and 128 padded rows x nc) as split GEMMs
+      rows     bf16x3 only: pca_dgrad_res_kernel<true>, whose work units are `fbu` 128-frame blocks of one triangle block; the last
+               unit of a triangle block is partial unless fbu divides nc / 128.  (fbu itself is a trip count: 129 frames already
+               run two frame blocks in one unit.)"""
+    body, attn, regr = MIXED_TERMS[mode]
+    mc = 64 * nc
+    f = {}
+    if body:
+        f["conv3"] = "conv123_bf16_kernel"
+        if body == 1:
+            lstm = "freq_lstm_bf16_kernel<1>"
+        else:
+            lstm = f"freq_lstm_bf16p_v3_kernel<persistent, {3 if body == 6 else 2} planes>, " + \
+                   ("one round of the tile queue" if 2 * nc <= cus else "several rounds of the tile queue")
+        f["freq"] = lstm + " + " + split_gemm_form(body, 256, mc, cus)
+        nt = 1 if body == 6 or (nc // 64) * 2 < 256 else 2
+        f["bilstm"] = split_gemm_form(body, 2048, mc, cus) + f" + time_lstm_bf16_kernel<{nt},{body}>"
+    if attn:
+        f["z"] = split_gemm_form(attn, 512, nc, cus) + " + " + split_gemm_form(attn, 128, nc, cus) + " + " + \
+                 ("the fp32 attention kernels" if attn == 6 else f"attn_key_score_kernel<{attn}>+attn_kernel<true> ts_shift={key_score_ts_shift(nc, cus)}")
+    if regr:
+        f["coef"] = " + ".join(sorted({split_gemm_form(regr, p, nc, cus) for p in (512, 256, 128)}))
+    if mode == "bf16x3":
+        nfb = nc // 128
+        fbu = 16 if PCA_TRIANGLE_BLOCKS * ((nfb + 15) // 16) >= 4 * cus else 8 if PCA_TRIANGLE_BLOCKS * ((nfb + 7) // 8) >= 4 * cus else 4
+        f["rows"] = "pca_dgrad_res_kernel<true>, " + ("last unit partial" if nfb % fbu else "whole units")
+    return f
+
+
+def offsets_expand_form(mode, nc, cus):
+    """The offsets head's PCA expansion in a split mode: a GEMM of nc rows by 15,104 = 59 x 256 padded columns (api_forward.cpp expand_rows)."""
+    return split_gemm_form(MIXED_TERMS[mode][2], nc, 15104, cus)
 
 
 def sizes_for(cus):

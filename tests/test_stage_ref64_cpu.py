@@ -80,6 +80,21 @@ def test_perturbations_touch_only_what_they_name(chain):
     assert float(diff.max()) <= 1e-12
 
 
+def test_bf16_basis_is_off_by_default_and_moves_the_rows(chain):
+    """StageRef64.expand(bf16_basis=True), the lost-low-terms control of tests/test_gpu_stage_mixed_ref64.py: the default is bitwise
+    what it was, the option moves every frame's rows by about a bf16 rounding of the basis (2^-9 relative per product) and leaves a
+    row of zero coefficients -- the means alone -- untouched."""
+    _, ref, st = chain
+    coef, rows = torch.from_numpy(st["coef"]), torch.from_numpy(st["rows"])
+    plain = torch.cat([(coef[:, :85] @ ref.pca_s[0].T + ref.pca_s[1]).reshape(8, -1, 6),
+                       (coef[:, 85:] @ ref.pca_r[0].T + ref.pca_r[1]).reshape(8, -1, 3)], -1).reshape(8, -1)
+    assert torch.equal(ref.expand(coef), rows) and torch.equal(ref.expand(coef, bf16_basis=False), rows) and torch.equal(plain, rows)
+    moved = (ref.expand(coef, bf16_basis=True) - rows).abs().amax(1) / float(rows.abs().max())
+    assert 1e-5 < float(moved.min()) and float(moved.max()) < 1e-2, moved
+    zero = torch.zeros(1, 265, dtype=torch.float64)
+    assert torch.equal(ref.expand(zero, bf16_basis=True), ref.expand(zero))
+
+
 # ------------------------------------------------------------------------------------------------------------- offsets head
 @pytest.fixture(scope="module")
 def offsets_chain(golden, synth_sd):
@@ -112,6 +127,14 @@ def test_offsets_regressor_reads_its_speaker(offsets_chain):
     assert np.abs(c5 - st["coef"]).max() > 1e-4
     mixed = ref.regress(z, torch.tensor([2, 5, 2, 5])).numpy()
     assert np.abs(mixed[0::2] - st["coef"][0::2]).max() <= 1e-12 and np.abs(mixed[1::2] - c5[1::2]).max() <= 1e-12
+
+
+def test_offsets_bf16_basis_is_off_by_default_and_moves_the_rows(offsets_chain):
+    _, ref, st = offsets_chain
+    coef, rows = torch.from_numpy(st["coef"]), torch.from_numpy(st["rows"])
+    assert torch.equal(ref.expand(coef), rows)
+    moved = (ref.expand(coef, bf16_basis=True) - rows).abs().amax(1) / float(rows.abs().max())
+    assert 1e-5 < float(moved.min()) and float(moved.max()) < 1e-2, moved
 
 
 def test_offsets_missing_mean_touches_only_its_column(offsets_chain):
