@@ -134,6 +134,8 @@ FramePos frame_pos(double idx, int sample_rate, int fps, int64_t sliding, int ts
 
 }  // namespace
 
+int sdfa_frontend_consts(int sample_rate, FrontendConsts &c) { return frontend_consts(sample_rate, c); }
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------

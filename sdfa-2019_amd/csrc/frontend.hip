@@ -21,6 +21,7 @@
 // wave's instructions in order); the workgroup meets at two barriers: window staged, mel image complete.
 #include "common.h"
 #include "kernels.h"
+#include "../../include/sdfa_augment.h"
 
 namespace {
 
@@ -1039,6 +1040,193 @@ __global__ __launch_bounds__(256) void ring_append_kernel(float *__restrict__ ri
     }
 }
 
+// ---------------------------------------------------------------------------- augmented training windows (include/sdfa_augment.h)
+// The training branch of windowed_features (get_features.py:8-223) on frontend_kernel's plan: one workgroup per window, the cut
+// staged once in LDS, column pairs through fft_pair_to_mel, delta filters and (T,F,C) store from an LDS image.  What is new sits
+// around those stages: the cut is T = 64 + 2 ex_time columns long, takes additive noise and a per-window pre-emphasis coefficient;
+// between the mel image and the deltas the image is edited in frequency (a row MAP, nothing is moved), resized bilinearly to
+// 128 x 64 by OpenCV's INTER_LINEAR rule, scaled per band and has its dropped rows zeroed.  With neutral parameters every added
+// operation is exact (fractions 0, weights 1), so the rows are frontend_kernel's bit for bit.
+//   LDS (WIN = 1024 / 512): cut 71 hop + win floats 40,448 / 20,224 | FFT buffers 65,536 / 32,768 | twiddles 8,192 / 4,096 |
+//   Hamming 4,096 / 2,048 | mel image [72][128] 36,864 | mel table 4,608  = 159,744 / 100,608 bytes: one workgroup per CU, as
+//   frontend_kernel.  Once the STFT is done the cut's space holds the resize tables and the FFT buffers' space the resized image.
+constexpr int AUG_TMAX = 64 + 2 * SDFA_AUGMENT_EX_TIME_MAX;
+
+// The contract's separately rounded float32 operations.  __fmul_rn / __fadd_rn are plain operators to this compiler and -ffp-contract=fast
+// may fuse them (in this kernel it did: x - a * xm came out as one fma where frontend_kernel has a multiply and a subtraction); the
+// pragma, which fast-honor-pragmas obeys, is what keeps the roundings apart.
+__device__ __forceinline__ float preemph_rn(float x, float a, float xm) {
+#pragma clang fp contract(off)
+    const float p = a * xm;
+    return x - p;
+}
+// v0 (1 - f) + v1 f with g = 1 - f: two products and a sum, each rounded (OpenCV's hresize / vresize for float images)
+__device__ __forceinline__ float lerp_rn(float v0, float g, float v1, float f) {
+#pragma clang fp contract(off)
+    const float p0 = v0 * g, p1 = v1 * f;
+    return p0 + p1;
+}
+
+template <int WIN>
+__global__ __launch_bounds__(FE_THREADS) void frontend_augment_kernel(FrontendConsts c, const float *__restrict__ pcm,
+                                                               const int64_t *__restrict__ clip_off, const int64_t *__restrict__ clip_len,
+                                                               int n_clips, const sdfa_augment_desc *__restrict__ desc,
+                                                               const float *__restrict__ noise, int64_t noise_stride,
+                                                               const float *__restrict__ scale, float *__restrict__ out) {
+    constexpr int HOP = WIN / 8, SMAX = HOP * (AUG_TMAX - 1) + WIN, NR4 = WIN / 256;
+    __shared__ float sY[SMAX];
+    __shared__ float2 sFft[FE_WAVES][WIN];
+    __shared__ float2 sTw[WIN];
+    __shared__ float sHamm[WIN];
+    __shared__ float sMel[AUG_TMAX][128];
+    __shared__ int sBin0[128];
+    __shared__ float sW8[8][128];
+    static_assert(SMAX >= 6 * 128, "the resize tables live in the cut's space");
+    static_assert(sizeof(float2) * FE_WAVES * WIN >= sizeof(float) * 64 * 128, "the resized image lives in the FFT buffers' space");
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n = blockIdx.x;
+    const sdfa_augment_desc d = desc[n];
+    // a descriptor cannot take the kernel out of bounds: both extents are clamped, an unknown clip is an empty one
+    const int ex = d.ex_time < -SDFA_AUGMENT_EX_TIME_MAX ? -SDFA_AUGMENT_EX_TIME_MAX : (d.ex_time > SDFA_AUGMENT_EX_TIME_MAX ? SDFA_AUGMENT_EX_TIME_MAX : d.ex_time);
+    const int ef = d.ex_feat < -SDFA_AUGMENT_EX_FEAT_MAX ? -SDFA_AUGMENT_EX_FEAT_MAX : (d.ex_feat > SDFA_AUGMENT_EX_FEAT_MAX ? SDFA_AUGMENT_EX_FEAT_MAX : d.ex_feat);
+    const bool known = d.clip >= 0 && d.clip < n_clips;
+    const int64_t off = known ? clip_off[d.clip] : 0, len = known ? clip_len[d.clip] : 0;
+    const int T = 64 + 2 * ex, LEN = (T - 1) * HOP + WIN;             // columns and samples of the cut
+    const int64_t s0 = d.start - (int64_t)ex * HOP;                   // get_features.py:53
+    const float a = d.preemph;
+    const float *nz = noise ? noise + n * noise_stride : nullptr;
+
+    for (int i = tid; i < WIN; i += FE_THREADS) { sTw[i] = c.twiddle[i]; sHamm[i] = c.hamm[i]; }
+    for (int i = tid; i < 128; i += FE_THREADS) sBin0[i] = c.mel_bin0[i];
+    for (int i = tid; i < 1024; i += FE_THREADS) sW8[i >> 7][i & 127] = c.mel_w8[i];
+    // cut, zero pad, noise, pre-emphasis (fp32, one rounding per op as numpy does): frontend_kernel's loop with the noise added
+    for (int i = tid; i < LEN; i += FE_THREADS) {
+        const int64_t g = s0 + i, last = len > 0 ? len - 1 : 0;
+        float r0 = 0.f, rm = 0.f;
+        if (len > 0) {
+            r0 = pcm[off + (g < 0 ? 0 : (g > last ? last : g))];
+            rm = pcm[off + (g - 1 < 0 ? 0 : (g - 1 > last ? last : g - 1))];
+        }
+        float x = (g >= 0 && g < len) ? r0 : 0.f;
+        float xm = (i > 0 && g - 1 >= 0 && g - 1 < len) ? rm : 0.f;
+        if (nz) {                                                    // block-uniform
+            x = __fadd_rn(x, nz[i]);
+            xm = __fadd_rn(xm, nz[i > 0 ? i - 1 : 0]);
+        }
+        sY[i] = (i == 0) ? x : preemph_rn(x, a, xm);
+    }
+    __syncthreads();
+
+    // column pairs by the absolute hop index of the cut's first sample, as frontend_kernel
+    const int64_t hop_base = (s0 >= 0 ? s0 : s0 - (HOP - 1)) / HOP;         // floor division
+    const int odd = (int)(hop_base & 1);
+    const int njobs = T / 2 + odd;                                           // T is even: T / 2 pairs, or solo + T / 2 - 1 pairs + solo
+    float2 *buf = sFft[wave];
+    for (int it = 0; it < (AUG_TMAX / 2 + 1 + FE_WAVES - 1) / FE_WAVES; ++it) {   // up to 37 jobs over the waves
+        const int job = it * FE_WAVES + wave;
+        const bool live = job < njobs;
+        int t0 = 2 * job - odd, t1 = t0 + 1;
+        if (!live) { t0 = 0; t1 = 1; }
+        const bool has0 = t0 >= 0, has1 = t1 <= T - 1;
+        const float *ya = sY + (has0 ? t0 : 0) * HOP, *yb = sY + (has1 ? t1 : T - 1) * HOP;
+        const float ga = has0 ? 1.f : 0.f, gb = has1 ? 1.f : 0.f;
+        float2 v[NR4][4];
+#pragma unroll
+        for (int b = 0; b < NR4; ++b) {
+            const int j = lane + 64 * b;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int nidx = j + r * (WIN / 4);
+                const float w = sHamm[nidx];
+                v[b][r] = make_float2(ga * (w * ya[nidx]), gb * (w * yb[nidx]));
+            }
+        }
+        float mel[2][2];
+        fft_pair_to_mel<WIN>(v, buf, sTw, sBin0, sW8, lane, mel);
+#pragma unroll
+        for (int col = 0; col < 2; ++col)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+                const int tt = col ? t1 : t0;
+                if (live && tt >= 0 && tt <= T - 1) sMel[tt][lane + 64 * bb] = mel[col][bb];
+            }
+    }
+    __syncthreads();   // mel image complete; the cut and the FFT buffers are free
+
+    // ---- resize tables in the cut's space.  Columns: source pair (x0, x1) and fraction of each of the 64 output columns.  Rows:
+    // the same for the 128 output rows over the R virtual rows, each virtual row mapped on a mel row or -1 (a row of zeros).
+    int *sX0 = reinterpret_cast<int *>(sY), *sX1 = sX0 + 128, *sR0 = sX0 + 256, *sR1 = sX0 + 384;
+    float *sFx = sY + 512, *sFy = sY + 640;
+    const bool lower = d.flags & SDFA_AUGMENT_LOWER_FREQ, trunck = d.flags & SDFA_AUGMENT_TRUNCK, reflect = d.flags & SDFA_AUGMENT_PAD_REFLECT;
+    const int R = ef < 0 ? 128 + ef : (ef > 0 && !trunck ? 128 + ef : 128);
+    // virtual row vr is mel row vr + shift: below 0 a row of zeros, above 127 the reflection 254 - p or zeros (get_features.py:125-140)
+    const int shift = ef < 0 ? (lower ? -ef : 0) : (lower ? -ef : (trunck ? ef : 0));
+    if (tid < 192) {
+        const bool row = tid >= 64;
+        const int o = row ? tid - 64 : tid, n_in = row ? R : T;
+        const double sc = (double)n_in / (row ? 128.0 : 64.0);
+        float f = (float)(((double)o + 0.5) * sc - 0.5);
+        int i0 = (int)floorf(f);
+        f -= (float)i0;
+        if (i0 < 0) { i0 = 0; f = 0.f; }
+        if (i0 >= n_in - 1) { i0 = n_in - 1; f = 0.f; }
+        const int i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
+        if (row) {
+            int p0 = i0 + shift, p1 = i1 + shift;
+            p0 = p0 < 0 ? -1 : (p0 > 127 ? (reflect ? 254 - p0 : -1) : p0);
+            p1 = p1 < 0 ? -1 : (p1 > 127 ? (reflect ? 254 - p1 : -1) : p1);
+            sR0[o] = p0; sR1[o] = p1; sFy[o] = f;
+        } else {
+            sX0[o] = i0; sX1[o] = i1; sFx[o] = f;
+        }
+    }
+    __syncthreads();
+    // ---- resize (time axis, then frequency axis), band gain, dropout -> the 64 x 128 image in the FFT buffers' space
+    float (*sImg)[128] = reinterpret_cast<float (*)[128]>(&sFft[0][0]);
+    {   // a thread keeps one band (FE_THREADS is a multiple of 128) and walks the columns: everything of the row is read once
+        const int f = tid & 127;
+        const int p0 = sR0[f], p1 = sR1[f];
+        const float fy = sFy[f], gy = __fsub_rn(1.f, fy);
+        const float gain = scale ? scale[n * 128 + f] : 1.f;
+        const uint32_t word = (f >> 5) == 0 ? d.drop[0] : ((f >> 5) == 1 ? d.drop[1] : ((f >> 5) == 2 ? d.drop[2] : d.drop[3]));
+        const bool dropped = (word >> (f & 31)) & 1u;
+        for (int t = tid >> 7; t < 64; t += FE_THREADS / 128) {
+            const int x0 = sX0[t], x1 = sX1[t];
+            const float fx = sFx[t], gx = __fsub_rn(1.f, fx);
+            const float h0 = p0 < 0 ? 0.f : lerp_rn(sMel[x0][p0], gx, sMel[x1][p0], fx);
+            const float h1 = p1 < 0 ? 0.f : lerp_rn(sMel[x0][p1], gx, sMel[x1][p1], fx);
+            float val = lerp_rn(h0, gy, h1, fy);
+            if (scale) val = val * gain;
+            sImg[t][f] = dropped ? 0.f : val;
+        }
+    }
+    __syncthreads();
+    // ---- Savitzky-Golay deltas + (T,F,C) store: frontend_kernel's
+    const float c2[9] = {28.f / 462.f, 7.f / 462.f, -8.f / 462.f, -17.f / 462.f, -20.f / 462.f,
+                         -17.f / 462.f, -8.f / 462.f, 7.f / 462.f, 28.f / 462.f};
+    float4 *dst = reinterpret_cast<float4 *>(out + n * (64 * 128 * 3));
+    for (int i4 = tid; i4 < 64 * 128 / 4; i4 += FE_THREADS) {
+        const int t = i4 >> 5, f0 = (i4 & 31) * 4;
+        const int tc = t < 4 ? 4 : (t > 59 ? 59 : t);
+        float m[4], d1[4], d2[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int j = -4; j <= 4; ++j) {
+                const float mv = sImg[tc + j][f0 + q];
+                s1 += (float)j * (1.0f / 60.0f) * mv;
+                s2 += c2[j + 4] * mv;
+            }
+            m[q] = sImg[t][f0 + q]; d1[q] = s1; d2[q] = s2;
+        }
+        dst[i4 * 3 + 0] = make_float4(m[0], d1[0], d2[0], m[1]);
+        dst[i4 * 3 + 1] = make_float4(d1[1], d2[1], m[2], d1[2]);
+        dst[i4 * 3 + 2] = make_float4(d2[2], m[3], d1[3], d2[3]);
+    }
+}
+
 }  // namespace
 
 extern thread_local int g_sdfa_mel_fft_radix4;   // api.cpp ("mel_fft_radix4"): 1 = the radix-4 / LDS-staged column FFT of rounds 2-3 at 16 kHz too
@@ -1171,5 +1359,21 @@ hipError_t sdfa_launch_gather_features(const float *mel_table, const int32_t *co
     const int64_t grid = chain ? span * 8 : n_frames;
     hipLaunchKernelGGL(gather_features_kernel, dim3((unsigned)grid), dim3(256), 0, s, reinterpret_cast<const float4 *>(mel_table),
                        col_to_u, Nc, n_frames, frame_major, chain, audio_feat);
+    return hipGetLastError();
+}
+
+hipError_t sdfa_launch_augment(const FrontendConsts &c, const float *pcm, const int64_t *clip_off, const int64_t *clip_len, int n_clips,
+                               const sdfa_augment_desc *desc, int64_t n, const float *noise, int64_t noise_stride, const float *scale,
+                               float *audio_feat, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (c.nbins_used > 256 || n > 0x7fffffff) return hipErrorInvalidValue;
+    if (c.win == 1024)
+        hipLaunchKernelGGL(frontend_augment_kernel<1024>, dim3((unsigned)n), dim3(FE_THREADS), 0, s, c, pcm, clip_off, clip_len, n_clips, desc,
+                           noise, noise_stride, scale, audio_feat);
+    else if (c.win == 512)
+        hipLaunchKernelGGL(frontend_augment_kernel<512>, dim3((unsigned)n), dim3(FE_THREADS), 0, s, c, pcm, clip_off, clip_len, n_clips, desc,
+                           noise, noise_stride, scale, audio_feat);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -80,6 +80,13 @@ struct FrontendConsts {      // device pointers, built once per sample rate
 hipError_t sdfa_launch_frontend(const FrontendConsts &c, const float *pcm, const int64_t *clip_off,
                                 const int64_t *clip_len, const int32_t *frame_clip, const int64_t *frame_start,
                                 int64_t n_frames, float *audio_feat, hipStream_t s);
+// augmented training windows (include/sdfa_augment.h): one workgroup per descriptor; noise / scale may be null
+struct sdfa_augment_desc;
+hipError_t sdfa_launch_augment(const FrontendConsts &c, const float *pcm, const int64_t *clip_off, const int64_t *clip_len, int n_clips,
+                               const sdfa_augment_desc *desc, int64_t n, const float *noise, int64_t noise_stride, const float *scale,
+                               float *audio_feat, hipStream_t s);
+// the constants of `sample_rate` on the current device (api_frontend.cpp: built on first use, then cached)
+int sdfa_frontend_consts(int sample_rate, FrontendConsts &c);
 // "spectral gather" form: mel columns of the DISTINCT STFT columns (col_src / n_distinct from the share map with
 // t in 1..63), then one gather + delta + store pass per frame
 hipError_t sdfa_launch_mel_columns(const FrontendConsts &c, const float *pcm, const int64_t *clip_off, const int64_t *clip_len,
