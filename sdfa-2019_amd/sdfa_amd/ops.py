@@ -9,6 +9,8 @@ host through PyTorch-ROCm custom ops"; SURVEY.md section 8(b) names them).
     torch.ops.sdfa.regress(z, speaker_id, model)                                          -> dgrad f32[N,89784] | offsets f32[N,15069]
     torch.ops.sdfa.regress_into(z, speaker_id, out, model)                                -> None (rows written into `out`; ids must be validated)
     torch.ops.sdfa.regress_coef(z, speaker_id, model)                                     -> PCA coefficients f32[N,265 | 59]
+    torch.ops.sdfa.objective(coef, truth, weight, model)                                  -> (loss f32[4], rec f64[2B,4], grad f32[2,2B,Kc])
+    torch.ops.sdfa.train_losses(coef, truth, weight, model)                               -> loss f32[4] = (ps, ms, pr, mr), differentiable in coef
 
 Thin by design: each op is the matching `Engine` method (ctypes call into libsdfa_hip.so on the current stream), registered
 with the dispatcher through `torch.library.custom_op` and given a fake-tensor shape function, so the ops compose with
@@ -174,6 +176,59 @@ def regress_coef(z: Tensor, speaker_id: Tensor, model: str) -> Tensor:
 @regress_coef.register_fake
 def _(z, speaker_id, model):
     return z.new_empty((z.shape[0], _model(model).coef_dim))
+
+
+# --------------------------------------------------------------------------------------------------- training objective
+def _bases(model):
+    """The PCA bases sdfa_amd.objective.attach_bases gave the model's engine (a KeyError that says so when it was never opted in)."""
+    from .objective import bases_of
+    return bases_of(_model(model))
+
+
+@custom_op("sdfa::objective", mutates_args=(), device_types="cuda")
+def objective(coef: Tensor, truth: Tensor, weight: Tensor, model: str) -> Tuple[Tensor, Tensor, Tensor]:
+    """sdfa_objective on the model's PCA bases: (loss f32[4] = (ps, ms, pr, mr), rec f64[2B,4], grad f32[2,2B,Kc]); one pass."""
+    from .objective import objective as _objective
+    return _objective(coef.contiguous(), truth.contiguous(), weight.contiguous(), _bases(model))
+
+
+@objective.register_fake
+def _(coef, truth, weight, model):
+    n, kc = coef.shape
+    return coef.new_empty((4,)), coef.new_empty((n, 4), dtype=torch.float64), coef.new_empty((2, n, kc))
+
+
+def combine_grads(grad_loss, grad, Ks):
+    """sum_i grad_loss[i] * d loss_i / d coef from the operator's grad [2][N][Kc]: the p term's scale and rotat columns take
+    grad_loss[0] and [2], the m term's [1] and [3]; a plain head (Ks = Kc) has no rotat columns.  Device arithmetic only."""
+    kr = grad.shape[2] - Ks
+    cp = torch.cat((grad_loss[0].expand(Ks), grad_loss[2].expand(kr)))
+    cm = torch.cat((grad_loss[1].expand(Ks), grad_loss[3].expand(kr)))
+    return grad[0] * cp + grad[1] * cm
+
+
+def _objective_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[2])
+    ctx.model = inputs[3]
+
+
+def _objective_backward(ctx, grad_loss, grad_rec, grad_grad):
+    (grad,) = ctx.saved_tensors
+    if grad_loss is None:
+        return None, None, None, None
+    return combine_grads(grad_loss, grad, _bases(ctx.model).Ks), None, None, None
+
+
+objective.register_autograd(_objective_backward, setup_context=_objective_setup)
+
+# train_losses: the four losses alone, differentiable with respect to coef through sdfa::objective (whose forward has already
+# computed and saved the gradients: backward is 2 x N x Kc elementwise work)
+torch.library.define("sdfa::train_losses", "(Tensor coef, Tensor truth, Tensor weight, str model) -> Tensor")
+
+
+@torch.library.impl("sdfa::train_losses", "CompositeImplicitAutograd")
+def train_losses(coef, truth, weight, model):
+    return torch.ops.sdfa.objective(coef, truth, weight, model)[0]
 
 
 class TraceableSpeechDrivenAnimation(torch.nn.Module):

@@ -1,8 +1,9 @@
 """SpeechDrivenAnimation / SaberSpeechDrivenAnimation -- inference surface of speech_anime/model/model.py.
 
 Same method names, arguments and result layouts as the reference; the arithmetic is libsdfa_hip.so.
-Not mirrored (out of scope): training (train_step, get_loss as a training objective), TensorBoard hooks, titles and
-the multi-source grid of the evaluate video.  get_loss's validation scalars are validate() (sdfa_amd.score).  evaluate() writes the dgrad track, .obj files with a template mesh and, with save_video, an
+Not mirrored (out of scope): the training loop (train_step, the encoder's backward, the optimiser), TensorBoard hooks,
+titles and the multi-source grid of the evaluate video.  get_loss is the training objective on PCA coefficients
+(sdfa_amd.objective); its validation scalars over whole clips are validate() (sdfa_amd.score).  evaluate() writes the dgrad track, .obj files with a template mesh and, with save_video, an
 .avi rendered on the GPU (sdfa_amd.render, speech_anime.video).
 """
 import os
@@ -78,6 +79,8 @@ class SaberSpeechDrivenAnimation:
         self._emotions_dict = deepcopy(dict(hparams.dataset_anime.emotions))
         self.current_epoch = 0
         self.on_gpu = True
+        self.training = False
+        self._loss_scalers = dict()      # DynamicLossScaler by the reference's name (dyn_p_scale, ...), made on first use
 
     # ---- weights ------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict=True):
@@ -87,6 +90,12 @@ class SaberSpeechDrivenAnimation:
         return self
 
     def eval(self):
+        self.training = False
+        return self
+
+    def train(self, mode=True):
+        """Only get_loss looks at it: in training the DynamicLossScalers update."""
+        self.training = bool(mode)
         return self
 
     def clear_signal_cache(self):
@@ -117,6 +126,68 @@ class SaberSpeechDrivenAnimation:
             data = torch.cat((scale.reshape(*scale.shape[:-1], -1, 6), rotat.reshape(*rotat.shape[:-1], -1, 3)), dim=-1)
             return data.reshape(*data.shape[:-2], -1)
         return tensor_dict[self._face_type]
+
+    # ---- model.py:261-330 ---------------------------------------------------------------------
+    def _train_losses(self, coef, truth, weight):
+        """(ps, ms, pr, mr) as a differentiable float32 [4] on the device (sdfa_amd/ops.py)."""
+        return torch.ops.sdfa.train_losses(coef, truth, weight, self._model._key)
+
+    def enable_training_objective(self, state_dict):
+        """Put the head's plain PCA bases (`state_dict`: the one given to load_state_dict, or a sdfa_amd.pca result under the
+        reference's names) on the device, once; get_loss needs it.  Inference-only use never pays for it."""
+        from sdfa_amd.objective import attach_bases
+        if self._model._engine is None:
+            raise RuntimeError("no weights loaded: call load_state_dict first")
+        attach_bases(self._model._engine, state_dict)
+        return self
+
+    def _scaler(self, name):
+        from sdfa_amd.objective import DynamicLossScaler
+        if name not in self._loss_scalers:
+            self._loss_scalers[name] = DynamicLossScaler()
+        return self._loss_scalers[name]
+
+    def get_loss(self, pred_dict, batch):
+        """The reference's objective for prediction_type "face_data" with a frozen PCA (pca_trainable = False), taken on
+        the PCA coefficients: pred_dict["prediction"] holds them under "dgrad_3d_coef" (N, Ks + Kr; scale first, as
+        sdfa::regress_coef writes them) or "{face_data_type}_coef" (N, K) for the offsets head; `batch` is what
+        DatasetSlidingWindow.train_batch returns ("face_data" (2B, W), "audio_feat", and the weights named by
+        hparams.loss.anime_loss_weight -- None means ones); enable_training_objective(state_dict) must have been called.
+        Returns (losses, scalars) with the reference's keys:
+        dyn_ps / dyn_ms / dyn_pr / dyn_mr (hparams.loss.dynamic_scalar, the default) or loss_ps / ..., dyn_ploss / dyn_mloss or
+        loss_ploss / loss_mloss for the offsets head, each times ploss_scale / mloss_scale; scalar_ps, scalar_ms, scalar_pr,
+        scalar_mr, scalar_ploss, scalar_mloss.  `losses` are differentiable device scalars whose sum is the objective; their
+        backward reaches the coefficients.  The four values are read back once (the reference reads each with .item()).
+        ELoss is absent: this model emits no evector."""
+        hp = self.hp.get("loss") or {}
+        dynamic = bool(hp.get("dynamic_scalar", True))
+        p_scale, m_scale = float(hp.get("ploss_scale", 1)), float(hp.get("mloss_scale", 1))
+        dgrad = self._face_type == "dgrad_3d"
+        coef = pred_dict["prediction"]["dgrad_3d_coef" if dgrad else f"{self._face_type}_coef"]
+        truth = batch["face_data"]
+        wkey = hp.get("anime_loss_weight")
+        weight = batch[wkey] if wkey is not None else torch.ones(coef.shape[0], dtype=torch.float32, device=coef.device)
+        loss4 = self._train_losses(coef, truth, weight)
+        vals = [float(v) for v in loss4.detach().cpu().tolist()]
+        losses, scalars = dict(), dict()
+        if dgrad:
+            terms = (("ps", "dyn_p_scale", p_scale), ("ms", "dyn_m_scale", m_scale), ("pr", "dyn_p_rotat", p_scale), ("mr", "dyn_m_rotat", m_scale))
+            for i, (name, _, _) in enumerate(terms):
+                scalars["scalar_" + name] = vals[i]
+            scalars["scalar_ploss"] = scalars["scalar_ps"] + scalars["scalar_pr"]
+            scalars["scalar_mloss"] = scalars["scalar_ms"] + scalars["scalar_mr"]
+        else:
+            terms = (("ploss", "dyn_p", p_scale), ("mloss", "dyn_m", m_scale))
+            scalars["scalar_ploss"], scalars["scalar_mloss"] = vals[0], vals[1]
+        for i, (name, scaler, mult) in enumerate(terms):
+            if dynamic:
+                sc = self._scaler(scaler)
+                if self.training:
+                    sc.update(vals[i])
+                losses["dyn_" + name] = loss4[i] / sc.scale * mult
+            else:
+                losses["loss_" + name] = loss4[i] * mult
+        return losses, scalars
 
     # ---- model.py:333-420 ---------------------------------------------------------------------
     @staticmethod
