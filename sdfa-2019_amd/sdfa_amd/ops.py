@@ -11,6 +11,8 @@ host through PyTorch-ROCm custom ops"; SURVEY.md section 8(b) names them).
     torch.ops.sdfa.regress_coef(z, speaker_id, model)                                     -> PCA coefficients f32[N,265 | 59]
     torch.ops.sdfa.objective(coef, truth, weight, model)                                  -> (loss f32[4], rec f64[2B,4], grad f32[2,2B,Kc])
     torch.ops.sdfa.train_losses(coef, truth, weight, model)                               -> loss f32[4] = (ps, ms, pr, mr), differentiable in coef
+    torch.ops.sdfa.head_train(z, speaker_id, trainer_key)                                 -> PCA coefficients f32[N,265 | 59] of a HeadTrainer's head;
+                                                                                             backward leaves the head's gradients in the trainer, returns dz
 
 Thin by design: each op is the matching `Engine` method (ctypes call into libsdfa_hip.so on the current stream), registered
 with the dispatcher through `torch.library.custom_op` and given a fake-tensor shape function, so the ops compose with
@@ -229,6 +231,35 @@ torch.library.define("sdfa::train_losses", "(Tensor coef, Tensor truth, Tensor w
 @torch.library.impl("sdfa::train_losses", "CompositeImplicitAutograd")
 def train_losses(coef, truth, weight, model):
     return torch.ops.sdfa.objective(coef, truth, weight, model)[0]
+
+
+# --------------------------------------------------------------------------------------------------- head training
+@custom_op("sdfa::head_train", mutates_args=(), device_types="cuda")
+def head_train(z: Tensor, speaker_id: Tensor, trainer_key: str) -> Tensor:
+    """sdfa_headtrain_forward of the HeadTrainer registered as `trainer_key` (sdfa_amd.headtrain.register_trainer): the
+    training forward of the regressor head, z f32[N,512] -> coef f32[N,Kc].  The head's parameters live in the trainer, not in
+    the graph: the backward needs z to require grad, runs sdfa_headtrain_backward, OVERWRITES the trainer's parameter
+    gradients and returns dz."""
+    from .headtrain import trainer_of
+    return trainer_of(trainer_key).forward(z.contiguous(), speaker_id)
+
+
+@head_train.register_fake
+def _(z, speaker_id, trainer_key):
+    from .headtrain import trainer_of
+    return z.new_empty((z.shape[0], trainer_of(trainer_key).coef_dim))
+
+
+def _head_train_setup(ctx, inputs, output):
+    ctx.trainer_key = inputs[2]
+
+
+def _head_train_backward(ctx, grad_coef):
+    from .headtrain import trainer_of
+    return trainer_of(ctx.trainer_key).backward(grad_coef.contiguous(), want_dz=True), None, None
+
+
+head_train.register_autograd(_head_train_backward, setup_context=_head_train_setup)
 
 
 class TraceableSpeechDrivenAnimation(torch.nn.Module):

@@ -1,8 +1,9 @@
 """SpeechDrivenAnimation / SaberSpeechDrivenAnimation -- inference surface of speech_anime/model/model.py.
 
 Same method names, arguments and result layouts as the reference; the arithmetic is libsdfa_hip.so.
-Not mirrored (out of scope): the training loop (train_step, the encoder's backward, the optimiser), TensorBoard hooks,
-titles and the multi-source grid of the evaluate video.  get_loss is the training objective on PCA coefficients
+Not mirrored (out of scope): the encoder's backward and with it the full training loop, TensorBoard hooks,
+titles and the multi-source grid of the evaluate video.  The regressor head alone trains with the encoder frozen: train_step,
+fit_head, head_state_dict and commit_head (sdfa_amd.headtrain).  get_loss is the training objective on PCA coefficients
 (sdfa_amd.objective); its validation scalars over whole clips are validate() (sdfa_amd.score).  evaluate() writes the dgrad track, .obj files with a template mesh and, with save_video, an
 .avi rendered on the GPU (sdfa_amd.render, speech_anime.video).
 """
@@ -188,6 +189,110 @@ class SaberSpeechDrivenAnimation:
             else:
                 losses["loss_" + name] = loss4[i] * mult
         return losses, scalars
+
+    # ---- fine-tuning the regressor head: model.py:109-113, saber_model.py:46-57, trainer.py:266-320 ----
+    def _head_optimizer_args(self):
+        """torch.optim.Adam's arguments from hparams.optim as saber_model.configure_optimizers reads them (default: the
+        model configurations' Adam(lr=1e-4, weight_decay=0)).  What the reference's configurations allow and this does not
+        build is refused by name."""
+        hp = self.hp
+        optim = hp.get("optim") or {}
+        args = dict(optim.get("args") or {})
+        args.pop("__entirety__", None)
+        trainer = hp.get("trainer") or {}
+        refusals = (
+            (optim.get("name", "Adam") != "Adam", f"optim.name = {optim.get('name')!r}: only Adam is built"),
+            (float(args.get("weight_decay", 0) or 0) != 0.0, f"optim.args.weight_decay = {args.get('weight_decay')!r}: weight decay is not built"),
+            (bool(args.get("amsgrad", False)), "optim.args.amsgrad: not built"),
+            (optim.get("lr_scheduler") is not None, "optim.lr_scheduler: schedulers are not built"),
+            (not hp.model.get("weight_norm", True), "model.weight_norm = False: the head is trained through its weight norm only"),
+            (trainer.get("max_grad_clip") is not None or trainer.get("max_grad_norm") is not None, "trainer.max_grad_clip / max_grad_norm: gradient clipping is not built"),
+            (int(trainer.get("grad_acc_steps", 1) or 1) > 1, f"trainer.grad_acc_steps = {trainer.get('grad_acc_steps')!r}: gradient accumulation is not built"),
+            (bool(((hp.model.get("output") or {}).get("pca_trainable", False))), "model.output.pca_trainable: a trainable PCA is not built"),
+        )
+        for bad, why in refusals:
+            if bad:
+                raise NotImplementedError("head training: " + why)
+        unknown = set(args) - {"lr", "betas", "eps", "weight_decay", "amsgrad"}
+        if unknown:
+            raise NotImplementedError(f"head training: optim.args {sorted(unknown)} are not built")
+        return dict(lr=float(args.get("lr", 1e-4)), betas=tuple(args.get("betas", (0.9, 0.999))), eps=float(args.get("eps", 1e-8)))
+
+    def enable_head_training(self, state_dict):
+        """Make the regressor head of `state_dict` (the one given to load_state_dict: weight_g / weight_v / bias under the
+        reference's names) trainable on the device, with the encoder frozen: a sdfa_amd.headtrain.HeadTrainer with the
+        reference's optimiser, and the PCA bases for get_loss.  The finalised inference engine stays read-only; commit_head()
+        makes a fresh one from the tuned head."""
+        from sdfa_amd.headtrain import HeadTrainer, register_trainer
+        self.enable_training_objective(state_dict)
+        head = "dgrad" if self._face_type == "dgrad_3d" else "offsets"
+        self._head_trainer = HeadTrainer(state_dict, head, device=self._model._engine.device, **self._head_optimizer_args())
+        self._head_trainer_key = register_trainer(self._head_trainer)
+        self._head_source = state_dict
+        return self
+
+    def _trainer(self):
+        tr = getattr(self, "_head_trainer", None)
+        if tr is None:
+            raise RuntimeError("head training is not enabled: call enable_head_training(state_dict) first")
+        return tr
+
+    def train_step(self, batch, i_batch):
+        """The reference's train_step (model.py:109-113) for the head: (pred_dict, loss_dict, scalars).  The frozen encoder runs
+        through torch.ops.sdfa.encoder without gradient, the head through torch.ops.sdfa.head_train; pred_dict["prediction"]
+        holds the coefficients under the key get_loss takes.  sum(loss_dict.values()).backward() leaves the head's gradients
+        in the trainer; optimizer_step() is the reference's optim.step()."""
+        tr = self._trainer()
+        self.train()
+        with torch.no_grad():
+            z, align = torch.ops.sdfa.encoder(batch["audio_feat"].contiguous(), self._model._key)
+        z = z.detach().requires_grad_(True)          # the head's parameters live in the trainer: the graph hangs on z, whose gradient is dz
+        coef = torch.ops.sdfa.head_train(z, batch["speaker_id"], self._head_trainer_key)
+        name = "dgrad_3d_coef" if self._face_type == "dgrad_3d" else f"{self._face_type}_coef"
+        pred_dict = dict(prediction={name: coef}, condition=z.view(-1, 1, 512), align_dict={"audio_encoder10": align.view(-1, 1, 64)}, latent_dict={})
+        loss_dict, scalars = self.get_loss(pred_dict, batch)
+        assert tr.coef_dim == coef.shape[1]
+        return pred_dict, loss_dict, scalars
+
+    def optimizer_step(self):
+        self._trainer().step()
+
+    def fit_head(self, trainset, steps, rng, batch_size=50, noise="device", fixed_batch=None):
+        """`steps` steps of the reference's loop (trainer.py:266-320: train_step, the summed losses' backward, optim.step) over
+        DatasetSlidingWindow.train_batch on `trainset` (a TrainSet); rng: numpy RandomState for the indices and the augmentation.
+        fixed_batch: train on this one batch instead.  Returns the scalars of every step."""
+        history = []
+        for i in range(int(steps)):
+            if fixed_batch is not None:
+                batch = fixed_batch
+            else:
+                idx = rng.randint(0, len(trainset), int(batch_size))
+                batch = DatasetSlidingWindow.train_batch(trainset, None, idx, rng, noise=noise, hparams=self.hp)
+            _, loss_dict, scalars = self.train_step(batch, i)
+            sum(loss_dict.values()).backward()
+            self.optimizer_step()
+            history.append(scalars)
+        return history
+
+    def head_state_dict(self):
+        """The tuned head under the reference's names ("_model._output_module. ... weight_g | weight_v | bias")."""
+        return self._trainer().head_state_dict()
+
+    def commit_head(self):
+        """A fresh inference engine from the original state dict with the tuned head in it, through the same weights.py route
+        as load_state_dict (the weight norm folded, strict shapes); generate_animation uses it from here on.  The trainer and
+        its Adam state stay as they are."""
+        tuned = self.head_state_dict()
+        src = self._head_source
+        prefixed = any(k.startswith("_model.") for k in src)
+        state = dict(src)
+        for k, v in tuned.items():
+            key = k if prefixed else k[len("_model."):]
+            assert key in state, key
+            state[key] = v
+        self.load_state_dict(state)
+        self.enable_training_objective(state)
+        return self
 
     # ---- model.py:333-420 ---------------------------------------------------------------------
     @staticmethod
