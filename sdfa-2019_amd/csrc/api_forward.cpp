@@ -163,12 +163,14 @@ int sdfa_model_set_reserved_cus(sdfa_model *m, int k) {
 
 // ------------------------------------------------------------------------------------------------
 static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,
-                        const int64_t *d_frame_start, int hop, float *d_z, float *d_align, void *d_workspace,
+                        const int64_t *d_frame_start, int hop, float *d_z, float *d_align, float *d_H, void *d_workspace,
                         int64_t workspace_bytes, void *stream) {
+    // d_H (sdfa_encoder_memory): every chunk's BiLSTM output leaves the K4 region as [n][64][512] before the next chunk reuses it;
+    // d_z may then be null.  Null for every other entry point, which launch what they always launched.
     if (!m || !m->finalized) return sdfa_fail(SDFA_ESTATE, "encoder_forward: model not finalised");
     if (n_frames == 0) return SDFA_OK;
-    if (!d_audio_feat || !d_z || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
-    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
+    if (!d_audio_feat || (!d_z && !d_H) || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
+    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z | (uintptr_t)d_H) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
     if ((uintptr_t)d_align & 3) return sdfa_fail(SDFA_EINVAL, "encoder_forward: d_align must be 4-byte aligned");
     const int64_t cap = capacity(workspace_bytes, m->keep);
     if (cap < 128) return sdfa_fail(SDFA_ENOSPACE, "encoder_forward: workspace of %lld bytes holds no 128-frame chunk", (long long)workspace_bytes);
@@ -317,7 +319,7 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
             ak.S = ws + w.KP;                                  // the partial scores take the first 8 Mc floats of the (unused) key-projection region
             ak.Nc = Nc; ak.Mc = Mc; ak.terms = at_terms == 6 ? 0 : at_terms; ak.reserve_cus = m->reserved_cus.load();
             if (tail_fused) {
-                ak.fuse_tail = 1; ak.Zk4 = ws + w.ZK; ak.z_out = d_z + f0 * 512; ak.align_out = d_align ? d_align + f0 * 64 : nullptr; ak.N = N;
+                ak.fuse_tail = 1; ak.Zk4 = ws + w.ZK; ak.z_out = d_z ? d_z + f0 * 512 : nullptr; ak.align_out = d_align ? d_align + f0 * 64 : nullptr; ak.N = N;
             }
             HIP_TRY(sdfa_launch_attn_key_score(ak, s));
         }
@@ -325,10 +327,11 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
 
         AttnArgs aa{};
         aa.KP = ws + w.KP; aa.QP = ws + w.QP; aa.H = ws + w.H1; aa.v = m->at_v; aa.b = m->at_b;
-        aa.Zk4 = ws + w.ZK; aa.z_out = d_z + f0 * 512; aa.align_out = d_align ? d_align + f0 * 64 : nullptr;
+        aa.Zk4 = ws + w.ZK; aa.z_out = d_z ? d_z + f0 * 512 : nullptr; aa.align_out = d_align ? d_align + f0 * 64 : nullptr;
         aa.N = N; aa.Nc = Nc; aa.Mc = Mc;
         aa.S = key_fused ? ws + w.KP : nullptr;
         pf.begin("attn"); if (!tail_fused) HIP_TRY(sdfa_launch_attn(aa, s)); pf.end();
+        if (d_H) HIP_TRY(sdfa_launch_tap(ws + w.H1, 3, N, Nc, d_H + f0 * (64 * 512), s));
     }
     return SDFA_OK;
 }
@@ -372,14 +375,21 @@ int sdfa_model_autotune(sdfa_model *m, int64_t n_frames, void *d_workspace, int6
 
 int sdfa_encoder_forward(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, float *d_z, float *d_align,
                          void *d_workspace, int64_t workspace_bytes, void *stream) {
-    return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, d_z, d_align, d_workspace, workspace_bytes, stream);
+    return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, d_z, d_align, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+// include/sdfa_attntrain.h: the frozen encoder's forward that also hands out the attention layer's memory
+int sdfa_encoder_memory(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, float *d_H, float *d_z, float *d_align,
+                        void *d_workspace, int64_t workspace_bytes, void *stream) {
+    if (!d_H) return sdfa_fail(SDFA_EINVAL, "encoder_memory: null pointer");
+    return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, d_z, d_align, d_H, d_workspace, workspace_bytes, stream);
 }
 
 int sdfa_encoder_forward_shared(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,
                                 const int64_t *d_frame_start, int hop, float *d_z, float *d_align, void *d_workspace,
                                 int64_t workspace_bytes, void *stream) {
     if (!d_frame_clip || !d_frame_start || hop <= 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward_shared: frame table missing");
-    return encoder_impl(m, d_audio_feat, n_frames, d_frame_clip, d_frame_start, hop, d_z, d_align, d_workspace, workspace_bytes, stream);
+    return encoder_impl(m, d_audio_feat, n_frames, d_frame_clip, d_frame_start, hop, d_z, d_align, nullptr, d_workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

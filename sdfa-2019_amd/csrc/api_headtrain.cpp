@@ -380,19 +380,7 @@ int sdfa_headtrain_adam(sdfa_headtrain *h, double lr, double beta1, double beta2
     if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
         return sdfa_fail(SDFA_EINVAL, "headtrain_adam: lr %g, betas (%g, %g), eps %g: torch.optim.Adam refuses these", lr, beta1, beta2, eps);
     const int64_t t = h->step + 1;
-    HtAdamArgs a;
-    a.p = h->d_param;
-    a.g = h->d_grad;
-    a.m = h->d_m;
-    a.v = h->d_v;
-    a.n = h->numel;
-    a.omb1 = (float)(1.0 - beta1);
-    a.beta2 = (float)beta2;
-    a.omb2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
-    a.step = (float)(lr / (1.0 - pow(beta1, (double)t)));
-    a.bc2s = (float)sqrt(1.0 - pow(beta2, (double)t));
-    HIP_TRY(headtrain_adam(a, (hipStream_t)stream));
+    HIP_TRY(headtrain_adam_step(h->d_param, h->d_grad, h->d_m, h->d_v, h->numel, t, lr, beta1, beta2, eps, (hipStream_t)stream));
     h->step = t;
     h->fwd_N = 0;                                           // the kept activations belong to the old parameters
     return SDFA_OK;

@@ -252,6 +252,25 @@ class Engine(FrontendOnly):
                                                   ws.numel(), _stream()))
         return z, align
 
+    def encoder_memory(self, audio_feat, want_z=True, want_align=True):
+        """(H (n,64,512), z (n,512) | None, align (n,64) | None): the encoder's forward that also writes the BiLSTM output the
+        attention layer reads (sdfa_encoder_memory, include/sdfa_attntrain.h); z and align are bitwise those of `encoder`."""
+        from . import attntrain  # noqa: F401  (binds the entry point)
+        assert audio_feat.is_cuda and audio_feat.dtype == torch.float32 and tuple(audio_feat.shape[1:]) == FEAT_SHAPE
+        audio_feat = audio_feat.contiguous()
+        n = audio_feat.shape[0]
+        H = torch.empty((n, 64, 512), dtype=torch.float32, device=self.device)
+        z = torch.empty((n, 512), dtype=torch.float32, device=self.device) if want_z else None
+        align = torch.empty((n, 64), dtype=torch.float32, device=self.device) if want_align else None
+        if n == 0:
+            return H, z, align
+        if self._autotune_pending and n >= self.AUTOTUNE_MIN_FRAMES:
+            self.autotune(n)
+        ws = self.workspace(n)
+        check(lib.sdfa_encoder_memory(self._m, _ptr(audio_feat), n, _ptr(H), _ptr(z) if want_z else None,
+                                      _ptr(align) if want_align else None, _ptr(ws), ws.numel(), _stream()))
+        return H, z, align
+
     @staticmethod
     def check_speaker_ids(speaker_id):
         """Raises what the reference's one_hot scatter_ raises for an id outside [0, 8) (saber/nn/functions.py:375-378).

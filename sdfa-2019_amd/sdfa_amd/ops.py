@@ -13,6 +13,9 @@ host through PyTorch-ROCm custom ops"; SURVEY.md section 8(b) names them).
     torch.ops.sdfa.train_losses(coef, truth, weight, model)                               -> loss f32[4] = (ps, ms, pr, mr), differentiable in coef
     torch.ops.sdfa.head_train(z, speaker_id, trainer_key)                                 -> PCA coefficients f32[N,265 | 59] of a HeadTrainer's head;
                                                                                              backward leaves the head's gradients in the trainer, returns dz
+    torch.ops.sdfa.encoder_memory(audio_feat, model)                                      -> (H f32[N,64,512], z f32[N,512], align f32[N,64]); z, align bitwise encoder's
+    torch.ops.sdfa.attn_train(H, trainer_key)                                             -> (z f32[N,512], align f32[N,64]) of an AttnTrainer's attention layer;
+                                                                                             backward leaves the layer's gradients in the trainer, returns dH (or None)
 
 Thin by design: each op is the matching `Engine` method (ctypes call into libsdfa_hip.so on the current stream), registered
 with the dispatcher through `torch.library.custom_op` and given a fake-tensor shape function, so the ops compose with
@@ -132,6 +135,19 @@ def encoder(audio_feat: Tensor, model: str) -> Tuple[Tensor, Tensor]:
 def _(audio_feat, model):
     n = audio_feat.shape[0]
     return audio_feat.new_empty((n, 512)), audio_feat.new_empty((n, 64))
+
+
+@custom_op("sdfa::encoder_memory", mutates_args=(), device_types="cuda")
+def encoder_memory(audio_feat: Tensor, model: str) -> Tuple[Tensor, Tensor, Tensor]:
+    """sdfa_encoder_memory: the encoder's forward that also returns H, the BiLSTM output [N][64][512] the attention layer reads."""
+    H, z, align = _model(model).encoder_memory(audio_feat)
+    return H, z, align
+
+
+@encoder_memory.register_fake
+def _(audio_feat, model):
+    n = audio_feat.shape[0]
+    return audio_feat.new_empty((n, 64, 512)), audio_feat.new_empty((n, 512)), audio_feat.new_empty((n, 64))
 
 
 @custom_op("sdfa::encoder_shared", mutates_args=(), device_types="cuda")
@@ -260,6 +276,39 @@ def _head_train_backward(ctx, grad_coef):
 
 
 head_train.register_autograd(_head_train_backward, setup_context=_head_train_setup)
+
+
+# --------------------------------------------------------------------------------------------------- attention training
+@custom_op("sdfa::attn_train", mutates_args=(), device_types="cuda")
+def attn_train(H: Tensor, trainer_key: str) -> Tuple[Tensor, Tensor]:
+    """sdfa_attntrain_forward of the AttnTrainer registered as `trainer_key` (sdfa_amd.attntrain.register_trainer): the training
+    forward of the attention layer, H f32[N,64,512] -> (z f32[N,512], align f32[N,64]).  The layer's parameters live in the
+    trainer, not in the graph: the backward needs H to require grad, runs sdfa_attntrain_backward, OVERWRITES the trainer's
+    parameter gradients and returns dH -- or None when the trainer has want_dH = False (nothing consumes dH yet).  align is not
+    differentiable through this operator."""
+    from .attntrain import trainer_of
+    return trainer_of(trainer_key).forward(H.contiguous())
+
+
+@attn_train.register_fake
+def _(H, trainer_key):
+    return H.new_empty((H.shape[0], 512)), H.new_empty((H.shape[0], 64))
+
+
+def _attn_train_setup(ctx, inputs, output):
+    ctx.trainer_key = inputs[1]
+    ctx.set_materialize_grads(False)       # an unused align arrives as None, not as zeros: a real gradient for it is refused
+
+
+def _attn_train_backward(ctx, grad_z, grad_align):
+    from .attntrain import trainer_of
+    if grad_align is not None:
+        raise NotImplementedError("sdfa::attn_train: align is not differentiable through this operator (a gradient for align was given)")
+    tr = trainer_of(ctx.trainer_key)
+    return tr.backward(grad_z.contiguous(), want_dH=getattr(tr, "want_dH", True)), None
+
+
+attn_train.register_autograd(_attn_train_backward, setup_context=_attn_train_setup)
 
 
 class TraceableSpeechDrivenAnimation(torch.nn.Module):

@@ -218,17 +218,27 @@ class SaberSpeechDrivenAnimation:
             raise NotImplementedError(f"head training: optim.args {sorted(unknown)} are not built")
         return dict(lr=float(args.get("lr", 1e-4)), betas=tuple(args.get("betas", (0.9, 0.999))), eps=float(args.get("eps", 1e-8)))
 
-    def enable_head_training(self, state_dict):
+    def enable_head_training(self, state_dict, attention=False):
         """Make the regressor head of `state_dict` (the one given to load_state_dict: weight_g / weight_v / bias under the
         reference's names) trainable on the device, with the encoder frozen: a sdfa_amd.headtrain.HeadTrainer with the
         reference's optimiser, and the PCA bases for get_loss.  The finalised inference engine stays read-only; commit_head()
-        makes a fresh one from the tuned head."""
+        makes a fresh one from the tuned head.
+
+        attention=True also trains the Bahdanau attention layer (layer 10 of the audio encoder) through a
+        sdfa_amd.attntrain.AttnTrainer with the same optimiser arguments and the same refusals: "attention + head, recurrent
+        stack frozen".  The recurrent stack runs in its inference form, without dropout."""
         from sdfa_amd.headtrain import HeadTrainer, register_trainer
         self.enable_training_objective(state_dict)
         head = "dgrad" if self._face_type == "dgrad_3d" else "offsets"
-        self._head_trainer = HeadTrainer(state_dict, head, device=self._model._engine.device, **self._head_optimizer_args())
+        optim = self._head_optimizer_args()
+        self._head_trainer = HeadTrainer(state_dict, head, device=self._model._engine.device, **optim)
         self._head_trainer_key = register_trainer(self._head_trainer)
         self._head_source = state_dict
+        self._attn_trainer = self._attn_trainer_key = None
+        if attention:
+            from sdfa_amd import attntrain
+            self._attn_trainer = attntrain.AttnTrainer(state_dict, device=self._model._engine.device, want_dH=False, **optim)   # nothing consumes dH yet
+            self._attn_trainer_key = attntrain.register_trainer(self._attn_trainer)
         return self
 
     def _trainer(self):
@@ -241,12 +251,23 @@ class SaberSpeechDrivenAnimation:
         """The reference's train_step (model.py:109-113) for the head: (pred_dict, loss_dict, scalars).  The frozen encoder runs
         through torch.ops.sdfa.encoder without gradient, the head through torch.ops.sdfa.head_train; pred_dict["prediction"]
         holds the coefficients under the key get_loss takes.  sum(loss_dict.values()).backward() leaves the head's gradients
-        in the trainer; optimizer_step() is the reference's optim.step()."""
+        in the trainer; optimizer_step() is the reference's optim.step().  With enable_head_training(attention=True) the frozen
+        stack runs through torch.ops.sdfa.encoder_memory and the attention layer through torch.ops.sdfa.attn_train, which also
+        gives align_dict; the backward then leaves the attention layer's gradients in its trainer as well."""
         tr = self._trainer()
         self.train()
-        with torch.no_grad():
-            z, align = torch.ops.sdfa.encoder(batch["audio_feat"].contiguous(), self._model._key)
-        z = z.detach().requires_grad_(True)          # the head's parameters live in the trainer: the graph hangs on z, whose gradient is dz
+        if getattr(self, "_attn_trainer", None) is not None:
+            # attention + head: the frozen stack up to the BiLSTM output H, then the two trained stages; dz flows from the head's
+            # backward into the attention layer's, whose parameter gradients stay in its trainer
+            with torch.no_grad():
+                H, _, _ = torch.ops.sdfa.encoder_memory(batch["audio_feat"].contiguous(), self._model._key)
+            H = H.detach().requires_grad_(True)
+            z, align = torch.ops.sdfa.attn_train(H, self._attn_trainer_key)
+            align = align.detach()
+        else:
+            with torch.no_grad():
+                z, align = torch.ops.sdfa.encoder(batch["audio_feat"].contiguous(), self._model._key)
+            z = z.detach().requires_grad_(True)      # the head's parameters live in the trainer: the graph hangs on z, whose gradient is dz
         coef = torch.ops.sdfa.head_train(z, batch["speaker_id"], self._head_trainer_key)
         name = "dgrad_3d_coef" if self._face_type == "dgrad_3d" else f"{self._face_type}_coef"
         pred_dict = dict(prediction={name: coef}, condition=z.view(-1, 1, 512), align_dict={"audio_encoder10": align.view(-1, 1, 64)}, latent_dict={})
@@ -255,7 +276,12 @@ class SaberSpeechDrivenAnimation:
         return pred_dict, loss_dict, scalars
 
     def optimizer_step(self):
-        self._trainer().step()
+        tr, at = self._trainer(), getattr(self, "_attn_trainer", None)
+        if at is not None and at.step_count != tr.step_count:
+            raise RuntimeError(f"head trainer at step {tr.step_count}, attention trainer at step {at.step_count}: they step together")
+        tr.step()
+        if at is not None:
+            at.step()
 
     def fit_head(self, trainset, steps, rng, batch_size=50, noise="device", fixed_batch=None):
         """`steps` steps of the reference's loop (trainer.py:266-320: train_step, the summed losses' backward, optim.step) over
@@ -275,8 +301,12 @@ class SaberSpeechDrivenAnimation:
         return history
 
     def head_state_dict(self):
-        """The tuned head under the reference's names ("_model._output_module. ... weight_g | weight_v | bias")."""
-        return self._trainer().head_state_dict()
+        """The tuned head under the reference's names ("_model._output_module. ... weight_g | weight_v | bias"), and with
+        attention training enabled the tuned attention tensors ("_model._audio_encoder._layers.10. ...")."""
+        tuned = self._trainer().head_state_dict()
+        if getattr(self, "_attn_trainer", None) is not None:
+            tuned.update(self._attn_trainer.attn_state_dict())
+        return tuned
 
     def commit_head(self):
         """A fresh inference engine from the original state dict with the tuned head in it, through the same weights.py route
