@@ -164,13 +164,15 @@ int sdfa_model_set_reserved_cus(sdfa_model *m, int k) {
 // ------------------------------------------------------------------------------------------------
 static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,
                         const int64_t *d_frame_start, int hop, float *d_z, float *d_align, float *d_H, void *d_workspace,
-                        int64_t workspace_bytes, void *stream) {
+                        int64_t workspace_bytes, void *stream, float *d_X1 = nullptr) {
     // d_H (sdfa_encoder_memory): every chunk's BiLSTM output leaves the K4 region as [n][64][512] before the next chunk reuses it;
     // d_z may then be null.  Null for every other entry point, which launch what they always launched.
+    // d_X1 (sdfa_encoder_layer0): every chunk's layer-0 output leaves its K4 region the same way, and the chunk ends there: no
+    // layer 1, no attention.  d_z, d_align and d_H are null then.
     if (!m || !m->finalized) return sdfa_fail(SDFA_ESTATE, "encoder_forward: model not finalised");
     if (n_frames == 0) return SDFA_OK;
-    if (!d_audio_feat || (!d_z && !d_H) || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
-    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z | (uintptr_t)d_H) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
+    if (!d_audio_feat || (!d_z && !d_H && !d_X1) || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
+    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z | (uintptr_t)d_H | (uintptr_t)d_X1) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
     if ((uintptr_t)d_align & 3) return sdfa_fail(SDFA_EINVAL, "encoder_forward: d_align must be 4-byte aligned");
     const int64_t cap = capacity(workspace_bytes, m->keep);
     if (cap < 128) return sdfa_fail(SDFA_ENOSPACE, "encoder_forward: workspace of %lld bytes holds no 128-frame chunk", (long long)workspace_bytes);
@@ -291,6 +293,11 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
             pf.end();
             pf.begin(lsn[l]); HIP_TRY(sdfa_launch_time_lstm(ta, s)); pf.end();
             xin = hout[l];
+            if (d_X1) break;
+        }
+        if (d_X1) {
+            HIP_TRY(sdfa_launch_tap(ws + w.H0, 3, N, Nc, d_X1 + f0 * (64 * 512), s));
+            continue;
         }
         // attention: proj_key over all 64 keys, Conv1d query over time steps 31..33, proj_qry
         const int at_terms = stage_terms(m, STAGE_ATTENTION);
@@ -383,6 +390,13 @@ int sdfa_encoder_memory(const sdfa_model *m, const float *d_audio_feat, int64_t 
                         void *d_workspace, int64_t workspace_bytes, void *stream) {
     if (!d_H) return sdfa_fail(SDFA_EINVAL, "encoder_memory: null pointer");
     return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, d_z, d_align, d_H, d_workspace, workspace_bytes, stream);
+}
+
+// include/sdfa_lstmtrain.h: the frozen encoder up to and including the BiLSTM's layer 0, whose output the trained layer 1 reads
+int sdfa_encoder_layer0(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, float *d_X1, void *d_workspace,
+                        int64_t workspace_bytes, void *stream) {
+    if (!d_X1) return sdfa_fail(SDFA_EINVAL, "encoder_layer0: null pointer");
+    return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, nullptr, nullptr, nullptr, d_workspace, workspace_bytes, stream, d_X1);
 }
 
 int sdfa_encoder_forward_shared(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,

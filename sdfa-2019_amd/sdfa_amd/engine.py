@@ -271,6 +271,22 @@ class Engine(FrontendOnly):
                                       _ptr(align) if want_align else None, _ptr(ws), ws.numel(), _stream()))
         return H, z, align
 
+    def encoder_layer0(self, audio_feat):
+        """X1 (n,64,512): the encoder up to and including layer 0 of the BiLSTM, the input of the layer sdfa_amd.lstmtrain trains
+        (sdfa_encoder_layer0, include/sdfa_lstmtrain.h); neither layer 1 nor the attention layer is launched."""
+        from . import lstmtrain  # noqa: F401  (binds the entry point)
+        assert audio_feat.is_cuda and audio_feat.dtype == torch.float32 and tuple(audio_feat.shape[1:]) == FEAT_SHAPE
+        audio_feat = audio_feat.contiguous()
+        n = audio_feat.shape[0]
+        X1 = torch.empty((n, 64, 512), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return X1
+        if self._autotune_pending and n >= self.AUTOTUNE_MIN_FRAMES:
+            self.autotune(n)
+        ws = self.workspace(n)
+        check(lib.sdfa_encoder_layer0(self._m, _ptr(audio_feat), n, _ptr(X1), _ptr(ws), ws.numel(), _stream()))
+        return X1
+
     @staticmethod
     def check_speaker_ids(speaker_id):
         """Raises what the reference's one_hot scatter_ raises for an id outside [0, 8) (saber/nn/functions.py:375-378).

@@ -16,6 +16,9 @@ host through PyTorch-ROCm custom ops"; SURVEY.md section 8(b) names them).
     torch.ops.sdfa.encoder_memory(audio_feat, model)                                      -> (H f32[N,64,512], z f32[N,512], align f32[N,64]); z, align bitwise encoder's
     torch.ops.sdfa.attn_train(H, trainer_key)                                             -> (z f32[N,512], align f32[N,64]) of an AttnTrainer's attention layer;
                                                                                              backward leaves the layer's gradients in the trainer, returns dH (or None)
+    torch.ops.sdfa.encoder_layer0(audio_feat, model)                                      -> X1 f32[N,64,512], the BiLSTM's layer-0 output (no layer 1, no attention)
+    torch.ops.sdfa.lstm_train(X, trainer_key)                                             -> Y f32[N,64,512] of an LstmTrainer's BiLSTM layer, X f32[N,64,256 | 512];
+                                                                                             backward leaves the layer's gradients in the trainer, returns dX (or None)
 
 Thin by design: each op is the matching `Engine` method (ctypes call into libsdfa_hip.so on the current stream), registered
 with the dispatcher through `torch.library.custom_op` and given a fake-tensor shape function, so the ops compose with
@@ -148,6 +151,17 @@ def encoder_memory(audio_feat: Tensor, model: str) -> Tuple[Tensor, Tensor, Tens
 def _(audio_feat, model):
     n = audio_feat.shape[0]
     return audio_feat.new_empty((n, 64, 512)), audio_feat.new_empty((n, 512)), audio_feat.new_empty((n, 64))
+
+
+@custom_op("sdfa::encoder_layer0", mutates_args=(), device_types="cuda")
+def encoder_layer0(audio_feat: Tensor, model: str) -> Tensor:
+    """sdfa_encoder_layer0: the encoder up to and including layer 0 of the BiLSTM, X1 [N][64][512], what the trained layer 1 reads."""
+    return _model(model).encoder_layer0(audio_feat)
+
+
+@encoder_layer0.register_fake
+def _(audio_feat, model):
+    return audio_feat.new_empty((audio_feat.shape[0], 64, 512))
 
 
 @custom_op("sdfa::encoder_shared", mutates_args=(), device_types="cuda")
@@ -284,7 +298,7 @@ def attn_train(H: Tensor, trainer_key: str) -> Tuple[Tensor, Tensor]:
     """sdfa_attntrain_forward of the AttnTrainer registered as `trainer_key` (sdfa_amd.attntrain.register_trainer): the training
     forward of the attention layer, H f32[N,64,512] -> (z f32[N,512], align f32[N,64]).  The layer's parameters live in the
     trainer, not in the graph: the backward needs H to require grad, runs sdfa_attntrain_backward, OVERWRITES the trainer's
-    parameter gradients and returns dH -- or None when the trainer has want_dH = False (nothing consumes dH yet).  align is not
+    parameter gradients and returns dH -- or None when the trainer has want_dH = False (no trained layer below consumes dH).  align is not
     differentiable through this operator."""
     from .attntrain import trainer_of
     return trainer_of(trainer_key).forward(H.contiguous())
@@ -309,6 +323,35 @@ def _attn_train_backward(ctx, grad_z, grad_align):
 
 
 attn_train.register_autograd(_attn_train_backward, setup_context=_attn_train_setup)
+
+
+# --------------------------------------------------------------------------------------------------- BiLSTM layer training
+@custom_op("sdfa::lstm_train", mutates_args=(), device_types="cuda")
+def lstm_train(X: Tensor, trainer_key: str) -> Tensor:
+    """sdfa_lstmtrain_forward of the LstmTrainer registered as `trainer_key` (sdfa_amd.lstmtrain.register_trainer): the training
+    forward of one bidirectional LSTM layer, X f32[N,64,I] -> Y f32[N,64,512].  The layer's parameters live in the trainer, not
+    in the graph: the backward needs X to require grad, runs sdfa_lstmtrain_backward, OVERWRITES the trainer's parameter
+    gradients and returns dX -- or None when the trainer has want_dX = False (the layer below is frozen)."""
+    from .lstmtrain import trainer_of
+    return trainer_of(trainer_key).forward(X.contiguous())
+
+
+@lstm_train.register_fake
+def _(X, trainer_key):
+    return X.new_empty((X.shape[0], 64, 512))
+
+
+def _lstm_train_setup(ctx, inputs, output):
+    ctx.trainer_key = inputs[1]
+
+
+def _lstm_train_backward(ctx, grad_Y):
+    from .lstmtrain import trainer_of
+    tr = trainer_of(ctx.trainer_key)
+    return tr.backward(grad_Y.contiguous(), want_dX=getattr(tr, "want_dX", True)), None
+
+
+lstm_train.register_autograd(_lstm_train_backward, setup_context=_lstm_train_setup)
 
 
 class TraceableSpeechDrivenAnimation(torch.nn.Module):

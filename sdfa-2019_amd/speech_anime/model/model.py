@@ -218,7 +218,7 @@ class SaberSpeechDrivenAnimation:
             raise NotImplementedError(f"head training: optim.args {sorted(unknown)} are not built")
         return dict(lr=float(args.get("lr", 1e-4)), betas=tuple(args.get("betas", (0.9, 0.999))), eps=float(args.get("eps", 1e-8)))
 
-    def enable_head_training(self, state_dict, attention=False):
+    def enable_head_training(self, state_dict, attention=False, bilstm_top=False, bilstm_dropout=0.0):
         """Make the regressor head of `state_dict` (the one given to load_state_dict: weight_g / weight_v / bias under the
         reference's names) trainable on the device, with the encoder frozen: a sdfa_amd.headtrain.HeadTrainer with the
         reference's optimiser, and the PCA bases for get_loss.  The finalised inference engine stays read-only; commit_head()
@@ -226,8 +226,21 @@ class SaberSpeechDrivenAnimation:
 
         attention=True also trains the Bahdanau attention layer (layer 10 of the audio encoder) through a
         sdfa_amd.attntrain.AttnTrainer with the same optimiser arguments and the same refusals: "attention + head, recurrent
-        stack frozen".  The recurrent stack runs in its inference form, without dropout."""
+        stack frozen".  The recurrent stack runs in its inference form, without dropout.
+
+        bilstm_top=True (with attention=True) also trains the top layer of the BiLSTM (layer 1 of layer 9 of the audio encoder;
+        DESIGN.md section 18) through a sdfa_amd.lstmtrain.LstmTrainer: the frozen stack ends at the layer-0 output, and the
+        attention layer's dH flows into the BiLSTM layer's backward.  bilstm_dropout = p > 0 is nn.LSTM's inter-layer dropout in
+        training mode (the reference trains with 0.1): the layer-0 output is multiplied by a Bernoulli keep mask over (1 - p),
+        drawn from self._train_generator, a torch.Generator on the device the caller may seed.  The default 0.0 is the
+        inference form, as above."""
         from sdfa_amd.headtrain import HeadTrainer, register_trainer
+        if bilstm_top and not attention:
+            raise NotImplementedError("head training: bilstm_top=True needs attention=True: the BiLSTM layer is trained through the attention layer's dH")
+        if not 0.0 <= float(bilstm_dropout) < 1.0:
+            raise ValueError(f"head training: bilstm_dropout = {bilstm_dropout!r} outside [0, 1)")
+        if float(bilstm_dropout) > 0.0 and not bilstm_top:
+            raise NotImplementedError("head training: bilstm_dropout needs bilstm_top=True: a frozen recurrent stack runs in its inference form")
         self.enable_training_objective(state_dict)
         head = "dgrad" if self._face_type == "dgrad_3d" else "offsets"
         optim = self._head_optimizer_args()
@@ -235,11 +248,26 @@ class SaberSpeechDrivenAnimation:
         self._head_trainer_key = register_trainer(self._head_trainer)
         self._head_source = state_dict
         self._attn_trainer = self._attn_trainer_key = None
+        self._lstm_trainer = self._lstm_trainer_key = None
+        self._bilstm_dropout = float(bilstm_dropout)
         if attention:
             from sdfa_amd import attntrain
-            self._attn_trainer = attntrain.AttnTrainer(state_dict, device=self._model._engine.device, want_dH=False, **optim)   # nothing consumes dH yet
+            # dH is consumed by the BiLSTM layer's backward, and by nothing without it
+            self._attn_trainer = attntrain.AttnTrainer(state_dict, device=self._model._engine.device, want_dH=bool(bilstm_top), **optim)
             self._attn_trainer_key = attntrain.register_trainer(self._attn_trainer)
+        if bilstm_top:
+            from sdfa_amd import lstmtrain
+            self._lstm_trainer = lstmtrain.LstmTrainer(state_dict, layer=1, device=self._model._engine.device, want_dX=False, **optim)   # layer 0 is frozen
+            self._lstm_trainer_key = lstmtrain.register_trainer(self._lstm_trainer)
         return self
+
+    def _bilstm_keep_mask(self, X1):
+        """nn.LSTM's inter-layer dropout in training mode: Bernoulli(1 - p) per element of the layer-0 output, over (1 - p)."""
+        p = self._bilstm_dropout
+        if getattr(self, "_train_generator", None) is None:
+            self._train_generator = torch.Generator(device=X1.device)
+        keep = torch.empty_like(X1).bernoulli_(1.0 - p, generator=self._train_generator)
+        return keep.div_(1.0 - p)
 
     def _trainer(self):
         tr = getattr(self, "_head_trainer", None)
@@ -253,10 +281,23 @@ class SaberSpeechDrivenAnimation:
         holds the coefficients under the key get_loss takes.  sum(loss_dict.values()).backward() leaves the head's gradients
         in the trainer; optimizer_step() is the reference's optim.step().  With enable_head_training(attention=True) the frozen
         stack runs through torch.ops.sdfa.encoder_memory and the attention layer through torch.ops.sdfa.attn_train, which also
-        gives align_dict; the backward then leaves the attention layer's gradients in its trainer as well."""
+        gives align_dict; the backward then leaves the attention layer's gradients in its trainer as well.  With bilstm_top=True
+        the frozen stack ends at the layer-0 output (torch.ops.sdfa.encoder_layer0), times the keep mask where bilstm_dropout
+        is set, and layer 1 of the BiLSTM runs through torch.ops.sdfa.lstm_train in front of the attention layer."""
         tr = self._trainer()
         self.train()
-        if getattr(self, "_attn_trainer", None) is not None:
+        if getattr(self, "_lstm_trainer", None) is not None:
+            # BiLSTM top layer + attention + head: dz flows from the head's backward into the attention layer's, its dH into the
+            # BiLSTM layer's; layer 0 and everything below are frozen, so no dX1 is formed
+            with torch.no_grad():
+                X1 = torch.ops.sdfa.encoder_layer0(batch["audio_feat"].contiguous(), self._model._key)
+                if self._bilstm_dropout > 0.0:
+                    X1 = X1 * self._bilstm_keep_mask(X1)
+            X1 = X1.detach().requires_grad_(True)
+            H = torch.ops.sdfa.lstm_train(X1, self._lstm_trainer_key)
+            z, align = torch.ops.sdfa.attn_train(H, self._attn_trainer_key)
+            align = align.detach()
+        elif getattr(self, "_attn_trainer", None) is not None:
             # attention + head: the frozen stack up to the BiLSTM output H, then the two trained stages; dz flows from the head's
             # backward into the attention layer's, whose parameter gradients stay in its trainer
             with torch.no_grad():
@@ -276,12 +317,16 @@ class SaberSpeechDrivenAnimation:
         return pred_dict, loss_dict, scalars
 
     def optimizer_step(self):
-        tr, at = self._trainer(), getattr(self, "_attn_trainer", None)
+        tr, at, lt = self._trainer(), getattr(self, "_attn_trainer", None), getattr(self, "_lstm_trainer", None)
         if at is not None and at.step_count != tr.step_count:
             raise RuntimeError(f"head trainer at step {tr.step_count}, attention trainer at step {at.step_count}: they step together")
+        if lt is not None and lt.step_count != tr.step_count:
+            raise RuntimeError(f"head trainer at step {tr.step_count}, BiLSTM trainer at step {lt.step_count}: they step together")
         tr.step()
         if at is not None:
             at.step()
+        if lt is not None:
+            lt.step()
 
     def fit_head(self, trainset, steps, rng, batch_size=50, noise="device", fixed_batch=None):
         """`steps` steps of the reference's loop (trainer.py:266-320: train_step, the summed losses' backward, optim.step) over
@@ -302,10 +347,13 @@ class SaberSpeechDrivenAnimation:
 
     def head_state_dict(self):
         """The tuned head under the reference's names ("_model._output_module. ... weight_g | weight_v | bias"), and with
-        attention training enabled the tuned attention tensors ("_model._audio_encoder._layers.10. ...")."""
+        attention training enabled the tuned attention tensors ("_model._audio_encoder._layers.10. ..."), with bilstm_top the
+        four tuned layer-1 tensors of the BiLSTM ("_model._audio_encoder._layers.9.weight_ih_l1 ...")."""
         tuned = self._trainer().head_state_dict()
         if getattr(self, "_attn_trainer", None) is not None:
             tuned.update(self._attn_trainer.attn_state_dict())
+        if getattr(self, "_lstm_trainer", None) is not None:
+            tuned.update(self._lstm_trainer.lstm_state_dict())
         return tuned
 
     def commit_head(self):
