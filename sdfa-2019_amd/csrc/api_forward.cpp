@@ -4,6 +4,7 @@
 #include "host.h"
 #include "kernels.h"
 #include "model.h"
+#include "../../include/sdfa_bilstm.h"
 
 #include <algorithm>
 
@@ -164,15 +165,17 @@ int sdfa_model_set_reserved_cus(sdfa_model *m, int k) {
 // ------------------------------------------------------------------------------------------------
 static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,
                         const int64_t *d_frame_start, int hop, float *d_z, float *d_align, float *d_H, void *d_workspace,
-                        int64_t workspace_bytes, void *stream, float *d_X1 = nullptr) {
+                        int64_t workspace_bytes, void *stream, float *d_X1 = nullptr, float *d_X0 = nullptr) {
     // d_H (sdfa_encoder_memory): every chunk's BiLSTM output leaves the K4 region as [n][64][512] before the next chunk reuses it;
     // d_z may then be null.  Null for every other entry point, which launch what they always launched.
     // d_X1 (sdfa_encoder_layer0): every chunk's layer-0 output leaves its K4 region the same way, and the chunk ends there: no
     // layer 1, no attention.  d_z, d_align and d_H are null then.
+    // d_X0 (sdfa_encoder_x0): every chunk's frequency projection leaves its K4 region as [n][64][256], and the chunk ends there: no
+    // BiLSTM.  The projection has to exist for every column then, so the chunk takes the expand-then-project order's first half.
     if (!m || !m->finalized) return sdfa_fail(SDFA_ESTATE, "encoder_forward: model not finalised");
     if (n_frames == 0) return SDFA_OK;
-    if (!d_audio_feat || (!d_z && !d_H && !d_X1) || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
-    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z | (uintptr_t)d_H | (uintptr_t)d_X1) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
+    if (!d_audio_feat || (!d_z && !d_H && !d_X1 && !d_X0) || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
+    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z | (uintptr_t)d_H | (uintptr_t)d_X1 | (uintptr_t)d_X0) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
     if ((uintptr_t)d_align & 3) return sdfa_fail(SDFA_EINVAL, "encoder_forward: d_align must be 4-byte aligned");
     const int64_t cap = capacity(workspace_bytes, m->keep);
     if (cap < 128) return sdfa_fail(SDFA_ENOSPACE, "encoder_forward: workspace of %lld bytes holds no 128-frame chunk", (long long)workspace_bytes);
@@ -266,9 +269,14 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         // projection is then never expanded at all.  (fp32 kernels; the bf16 recurrences and the debug taps, which read the
         // expanded projection, keep the expand-then-project order.)  The projected columns live in the frequency LSTM's hidden-state
         // region, which is dead once the projection above has read it.
-        const bool share_gx0 = share && !m->keep && stage_terms(m, STAGE_BODY) == 0 && !g_sdfa_share_gx0_off;
+        const bool share_gx0 = share && !m->keep && stage_terms(m, STAGE_BODY) == 0 && !g_sdfa_share_gx0_off && !d_X0;
         if (share && !share_gx0) {   // scatter every distinct column's 256 features to all the (t, n) columns that contain it
             pf.begin("share_expand"); HIP_TRY(sdfa_launch_expand_cols(ws + w.ZU, col_to_u, ws + w.Z, 64, Mc, s)); pf.end();
+        }
+
+        if (d_X0) {      // Z (X3's place where nothing is kept: the frequency LSTM has read X3) holds every column's projection
+            HIP_TRY(sdfa_launch_x0_rows(ws + w.Z, N, Nc, d_X0 + f0 * (64 * 256), s));
+            continue;
         }
 
         const float *xin = share_gx0 ? ws + w.ZU : ws + w.Z;
@@ -397,6 +405,15 @@ int sdfa_encoder_layer0(const sdfa_model *m, const float *d_audio_feat, int64_t 
                         int64_t workspace_bytes, void *stream) {
     if (!d_X1) return sdfa_fail(SDFA_EINVAL, "encoder_layer0: null pointer");
     return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, nullptr, nullptr, nullptr, d_workspace, workspace_bytes, stream, d_X1);
+}
+
+// include/sdfa_bilstm.h: the frozen encoder up to the BiLSTM's input, the 256-feature projection of every column as rows
+int sdfa_bilstm_abi_version(void) { return SDFA_BILSTM_ABI_VERSION; }
+
+int sdfa_encoder_x0(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, float *d_X0, void *d_workspace,
+                    int64_t workspace_bytes, void *stream) {
+    if (!d_X0) return sdfa_fail(SDFA_EINVAL, "encoder_x0: null pointer");
+    return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, nullptr, nullptr, nullptr, d_workspace, workspace_bytes, stream, nullptr, d_X0);
 }
 
 int sdfa_encoder_forward_shared(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,

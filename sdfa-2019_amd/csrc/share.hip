@@ -303,3 +303,24 @@ hipError_t sdfa_launch_expand_cols(const float *Zu, const int32_t *col_to_u, flo
                        reinterpret_cast<const float4 *>(Zu), col_to_u, reinterpret_cast<float4 *>(Z), nquads, Mc);
     return hipGetLastError();
 }
+
+// sdfa_encoder_x0 (include/sdfa_bilstm.h): the expanded frequency projection Z, K4 [64 quads][Mc], m = t*Nc + n  ->  rows
+// (n, 64 t, 256), what layer 0 of the BiLSTM reads.  (The debug tap of Z writes the reference's (n, 256, 64 t), the transpose of this.)
+// A block is one time step of four frames: a thread moves one quad, the four frames of a quad are read as one 64-byte run and a
+// frame's 16 quads of a wave are written as one 256-byte run.
+namespace {
+__global__ void __launch_bounds__(256) x0_rows_kernel(const float4 *__restrict__ src, int64_t N, int64_t Nc, float4 *__restrict__ dst) {
+    const int t = (int)(blockIdx.x & 63);
+    const int64_t n = (int64_t)(blockIdx.x >> 6) * 4 + (threadIdx.x & 3);
+    const int q = (int)(threadIdx.x >> 2);
+    if (n >= N) return;
+    dst[(n * 64 + t) * 64 + q] = src[(int64_t)q * 64 * Nc + (int64_t)t * Nc + n];
+}
+}  // namespace
+
+hipError_t sdfa_launch_x0_rows(const float *Z, int64_t N, int64_t Nc, float *dst, hipStream_t s) {
+    if (N < 1 || N > Nc || (N + 3) / 4 * 64 > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(x0_rows_kernel, dim3((unsigned)((N + 3) / 4 * 64)), dim3(256), 0, s, reinterpret_cast<const float4 *>(Z), N, Nc,
+                       reinterpret_cast<float4 *>(dst));
+    return hipGetLastError();
+}

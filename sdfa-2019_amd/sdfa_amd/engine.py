@@ -287,6 +287,22 @@ class Engine(FrontendOnly):
         check(lib.sdfa_encoder_layer0(self._m, _ptr(audio_feat), n, _ptr(X1), _ptr(ws), ws.numel(), _stream()))
         return X1
 
+    def encoder_x0(self, audio_feat):
+        """X0 (n,64,256): the encoder up to the BiLSTM's input, row (n, t) the 256 projected features of column t of frame n -- the
+        input of sdfa_amd.lstmtrain.LstmTrainer(layer=0) (sdfa_encoder_x0, include/sdfa_bilstm.h); no BiLSTM layer is launched."""
+        from . import bilstmtrain  # noqa: F401  (binds the entry point)
+        assert audio_feat.is_cuda and audio_feat.dtype == torch.float32 and tuple(audio_feat.shape[1:]) == FEAT_SHAPE
+        audio_feat = audio_feat.contiguous()
+        n = audio_feat.shape[0]
+        X0 = torch.empty((n, 64, 256), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return X0
+        if self._autotune_pending and n >= self.AUTOTUNE_MIN_FRAMES:
+            self.autotune(n)
+        ws = self.workspace(n)
+        check(lib.sdfa_encoder_x0(self._m, _ptr(audio_feat), n, _ptr(X0), _ptr(ws), ws.numel(), _stream()))
+        return X0
+
     @staticmethod
     def check_speaker_ids(speaker_id):
         """Raises what the reference's one_hot scatter_ raises for an id outside [0, 8) (saber/nn/functions.py:375-378).

@@ -17,7 +17,8 @@ host through PyTorch-ROCm custom ops"; SURVEY.md section 8(b) names them).
     torch.ops.sdfa.attn_train(H, trainer_key)                                             -> (z f32[N,512], align f32[N,64]) of an AttnTrainer's attention layer;
                                                                                              backward leaves the layer's gradients in the trainer, returns dH (or None)
     torch.ops.sdfa.encoder_layer0(audio_feat, model)                                      -> X1 f32[N,64,512], the BiLSTM's layer-0 output (no layer 1, no attention)
-    torch.ops.sdfa.lstm_train(X, trainer_key)                                             -> Y f32[N,64,512] of an LstmTrainer's BiLSTM layer, X f32[N,64,256 | 512];
+    torch.ops.sdfa.encoder_x0(audio_feat, model)                                          -> X0 f32[N,64,256], the BiLSTM's input (the frequency projection as rows; no BiLSTM)
+    torch.ops.sdfa.lstm_train(X, trainer_key)                                           -> Y f32[N,64,512] of an LstmTrainer's BiLSTM layer, X f32[N,64,256 | 512];
                                                                                              backward leaves the layer's gradients in the trainer, returns dX (or None)
 
 Thin by design: each op is the matching `Engine` method (ctypes call into libsdfa_hip.so on the current stream), registered
@@ -162,6 +163,17 @@ def encoder_layer0(audio_feat: Tensor, model: str) -> Tensor:
 @encoder_layer0.register_fake
 def _(audio_feat, model):
     return audio_feat.new_empty((audio_feat.shape[0], 64, 512))
+
+
+@custom_op("sdfa::encoder_x0", mutates_args=(), device_types="cuda")
+def encoder_x0(audio_feat: Tensor, model: str) -> Tensor:
+    """sdfa_encoder_x0: the encoder up to the BiLSTM's input, X0 [N][64][256], what the trained layer 0 reads."""
+    return _model(model).encoder_x0(audio_feat)
+
+
+@encoder_x0.register_fake
+def _(audio_feat, model):
+    return audio_feat.new_empty((audio_feat.shape[0], 64, 256))
 
 
 @custom_op("sdfa::encoder_shared", mutates_args=(), device_types="cuda")

@@ -218,7 +218,7 @@ class SaberSpeechDrivenAnimation:
             raise NotImplementedError(f"head training: optim.args {sorted(unknown)} are not built")
         return dict(lr=float(args.get("lr", 1e-4)), betas=tuple(args.get("betas", (0.9, 0.999))), eps=float(args.get("eps", 1e-8)))
 
-    def enable_head_training(self, state_dict, attention=False, bilstm_top=False, bilstm_dropout=0.0):
+    def enable_head_training(self, state_dict, attention=False, bilstm_top=False, bilstm_dropout=0.0, bilstm_bottom=False):
         """Make the regressor head of `state_dict` (the one given to load_state_dict: weight_g / weight_v / bias under the
         reference's names) trainable on the device, with the encoder frozen: a sdfa_amd.headtrain.HeadTrainer with the
         reference's optimiser, and the PCA bases for get_loss.  The finalised inference engine stays read-only; commit_head()
@@ -233,8 +233,14 @@ class SaberSpeechDrivenAnimation:
         attention layer's dH flows into the BiLSTM layer's backward.  bilstm_dropout = p > 0 is nn.LSTM's inter-layer dropout in
         training mode (the reference trains with 0.1): the layer-0 output is multiplied by a Bernoulli keep mask over (1 - p),
         drawn from self._train_generator, a torch.Generator on the device the caller may seed.  The default 0.0 is the
-        inference form, as above."""
+        inference form, as above.
+
+        bilstm_bottom=True (with bilstm_top=True) also trains the bottom layer of the BiLSTM through a
+        second LstmTrainer(layer=0): the frozen stack ends at the frequency projection (torch.ops.sdfa.encoder_x0), the top
+        layer's dX flows through the keep mask into the bottom layer's backward, and everything above the frequency LSTM trains."""
         from sdfa_amd.headtrain import HeadTrainer, register_trainer
+        if bilstm_bottom and not bilstm_top:
+            raise NotImplementedError("head training: bilstm_bottom=True needs bilstm_top=True: the bottom layer is trained through the top layer's dX")
         if bilstm_top and not attention:
             raise NotImplementedError("head training: bilstm_top=True needs attention=True: the BiLSTM layer is trained through the attention layer's dH")
         if not 0.0 <= float(bilstm_dropout) < 1.0:
@@ -249,7 +255,10 @@ class SaberSpeechDrivenAnimation:
         self._head_source = state_dict
         self._attn_trainer = self._attn_trainer_key = None
         self._lstm_trainer = self._lstm_trainer_key = None
+        self._lstm0_trainer = self._lstm0_trainer_key = None
         self._bilstm_dropout = float(bilstm_dropout)
+        self._train_flags = dict(attention=bool(attention), bilstm_top=bool(bilstm_top), bilstm_bottom=bool(bilstm_bottom),
+                                 bilstm_dropout=float(bilstm_dropout))
         if attention:
             from sdfa_amd import attntrain
             # dH is consumed by the BiLSTM layer's backward, and by nothing without it
@@ -257,8 +266,12 @@ class SaberSpeechDrivenAnimation:
             self._attn_trainer_key = attntrain.register_trainer(self._attn_trainer)
         if bilstm_top:
             from sdfa_amd import lstmtrain
-            self._lstm_trainer = lstmtrain.LstmTrainer(state_dict, layer=1, device=self._model._engine.device, want_dX=False, **optim)   # layer 0 is frozen
+            # dX1 is consumed by the bottom layer's backward, and by nothing while layer 0 is frozen
+            self._lstm_trainer = lstmtrain.LstmTrainer(state_dict, layer=1, device=self._model._engine.device, want_dX=bool(bilstm_bottom), **optim)
             self._lstm_trainer_key = lstmtrain.register_trainer(self._lstm_trainer)
+        if bilstm_bottom:
+            self._lstm0_trainer = lstmtrain.LstmTrainer(state_dict, layer=0, device=self._model._engine.device, want_dX=False, **optim)   # the frequency LSTM is frozen
+            self._lstm0_trainer_key = lstmtrain.register_trainer(self._lstm0_trainer)
         return self
 
     def _bilstm_keep_mask(self, X1):
@@ -283,10 +296,27 @@ class SaberSpeechDrivenAnimation:
         stack runs through torch.ops.sdfa.encoder_memory and the attention layer through torch.ops.sdfa.attn_train, which also
         gives align_dict; the backward then leaves the attention layer's gradients in its trainer as well.  With bilstm_top=True
         the frozen stack ends at the layer-0 output (torch.ops.sdfa.encoder_layer0), times the keep mask where bilstm_dropout
-        is set, and layer 1 of the BiLSTM runs through torch.ops.sdfa.lstm_train in front of the attention layer."""
+        is set, and layer 1 of the BiLSTM runs through torch.ops.sdfa.lstm_train in front of the attention layer.  With
+        bilstm_bottom=True the frozen stack ends at the BiLSTM's input (torch.ops.sdfa.encoder_x0) and both layers run through
+        torch.ops.sdfa.lstm_train, the keep mask between them inside the graph."""
         tr = self._trainer()
         self.train()
-        if getattr(self, "_lstm_trainer", None) is not None:
+        if getattr(self, "_lstm0_trainer", None) is not None:
+            # both BiLSTM layers + attention + head: dH flows into layer 1's backward, its dX1 through the keep mask (autograd's
+            # product rule: nn.LSTM's inter-layer dropout with both layers trained) into layer 0's; the frequency LSTM and
+            # everything below are frozen, so no dX0 is formed
+            with torch.no_grad():
+                X0 = torch.ops.sdfa.encoder_x0(batch["audio_feat"].contiguous(), self._model._key)
+            X0 = X0.detach().requires_grad_(True)
+            X1 = torch.ops.sdfa.lstm_train(X0, self._lstm0_trainer_key)
+            if self._bilstm_dropout > 0.0:
+                with torch.no_grad():
+                    keep = self._bilstm_keep_mask(X1)
+                X1 = X1 * keep
+            H = torch.ops.sdfa.lstm_train(X1, self._lstm_trainer_key)
+            z, align = torch.ops.sdfa.attn_train(H, self._attn_trainer_key)
+            align = align.detach()
+        elif getattr(self, "_lstm_trainer", None) is not None:
             # BiLSTM top layer + attention + head: dz flows from the head's backward into the attention layer's, its dH into the
             # BiLSTM layer's; layer 0 and everything below are frozen, so no dX1 is formed
             with torch.no_grad():
@@ -318,15 +348,20 @@ class SaberSpeechDrivenAnimation:
 
     def optimizer_step(self):
         tr, at, lt = self._trainer(), getattr(self, "_attn_trainer", None), getattr(self, "_lstm_trainer", None)
+        l0 = getattr(self, "_lstm0_trainer", None)
         if at is not None and at.step_count != tr.step_count:
             raise RuntimeError(f"head trainer at step {tr.step_count}, attention trainer at step {at.step_count}: they step together")
         if lt is not None and lt.step_count != tr.step_count:
             raise RuntimeError(f"head trainer at step {tr.step_count}, BiLSTM trainer at step {lt.step_count}: they step together")
+        if l0 is not None and l0.step_count != tr.step_count:
+            raise RuntimeError(f"head trainer at step {tr.step_count}, BiLSTM bottom-layer trainer at step {l0.step_count}: they step together")
         tr.step()
         if at is not None:
             at.step()
         if lt is not None:
             lt.step()
+        if l0 is not None:
+            l0.step()
 
     def fit_head(self, trainset, steps, rng, batch_size=50, noise="device", fixed_batch=None):
         """`steps` steps of the reference's loop (trainer.py:266-320: train_step, the summed losses' backward, optim.step) over
@@ -348,13 +383,56 @@ class SaberSpeechDrivenAnimation:
     def head_state_dict(self):
         """The tuned head under the reference's names ("_model._output_module. ... weight_g | weight_v | bias"), and with
         attention training enabled the tuned attention tensors ("_model._audio_encoder._layers.10. ..."), with bilstm_top the
-        four tuned layer-1 tensors of the BiLSTM ("_model._audio_encoder._layers.9.weight_ih_l1 ...")."""
+        four tuned layer-1 tensors of the BiLSTM ("_model._audio_encoder._layers.9.weight_ih_l1 ..."), with bilstm_bottom the
+        four layer-0 tensors ("... weight_ih_l0", "weight_hh_l0" and their "_reverse" twins)."""
         tuned = self._trainer().head_state_dict()
         if getattr(self, "_attn_trainer", None) is not None:
             tuned.update(self._attn_trainer.attn_state_dict())
         if getattr(self, "_lstm_trainer", None) is not None:
             tuned.update(self._lstm_trainer.lstm_state_dict())
+        if getattr(self, "_lstm0_trainer", None) is not None:
+            tuned.update(self._lstm0_trainer.lstm_state_dict())
         return tuned
+
+    # ---- save, stop, resume: what a training loop around train_step has to carry (DESIGN.md section 19) ----
+    _TRAINER_SLOTS = (("head", "_head_trainer"), ("attention", "_attn_trainer"), ("bilstm_top", "_lstm_trainer"), ("bilstm_bottom", "_lstm0_trainer"))
+
+    def training_state_dict(self):
+        """Everything a fit needs to continue bit for bit: every enabled trainer's state_dict() (parameters, both Adam moments,
+        the step count, the optimiser arguments) under "head", "attention", "bilstm_top", "bilstm_bottom"; the
+        DynamicLossScalers' state by the reference's names; the dropout generator's state (None while nothing has been drawn);
+        and the flags enable_head_training was called with.  Host data only, so torch.save takes it."""
+        self._trainer()
+        trainers = {name: getattr(self, attr).state_dict() for name, attr in self._TRAINER_SLOTS if getattr(self, attr, None) is not None}
+        gen = getattr(self, "_train_generator", None)
+        return dict(flags=dict(self._train_flags), trainers=trainers,
+                    scalers={name: sc.state_dict() for name, sc in self._loss_scalers.items()},
+                    generator=None if gen is None else gen.get_state().clone())
+
+    def load_training_state_dict(self, state):
+        """Continue from training_state_dict() on a model enabled with the same flags; a state taken with other flags is refused
+        by name, before anything is changed."""
+        self._trainer()
+        theirs, mine = dict(state["flags"]), self._train_flags
+        differ = [f"{k}={theirs.get(k)!r} (this model: {k}={mine[k]!r})" for k in mine if theirs.get(k) != mine[k]]
+        if differ or set(theirs) != set(mine):
+            raise ValueError("training state: taken with " + ", ".join(differ or sorted(set(theirs) ^ set(mine))) +
+                             ": enable_head_training must be called with the flags the state was taken with")
+        enabled = {name for name, attr in self._TRAINER_SLOTS if getattr(self, attr, None) is not None}
+        if set(state["trainers"]) != enabled:
+            raise ValueError(f"training state: holds the trainers {sorted(state['trainers'])}, this model has {sorted(enabled)}")
+        for name, attr in self._TRAINER_SLOTS:
+            if name in enabled:
+                getattr(self, attr).load_state_dict(state["trainers"][name])
+        self._loss_scalers = dict()
+        for name, sc in state["scalers"].items():
+            self._scaler(name).load_state_dict(sc)
+        if state.get("generator") is None:
+            self._train_generator = None
+        else:
+            self._train_generator = torch.Generator(device=self._model._engine.device)
+            self._train_generator.set_state(state["generator"])
+        return self
 
     def commit_head(self):
         """A fresh inference engine from the original state dict with the tuned head in it, through the same weights.py route
