@@ -1,15 +1,16 @@
-// Host side of the attention layer's training step (include/sdfa_attntrain.h): the handle and its flat
-// device buffers, the refusals, the workspace layout and the launches of attntrain.hip.  Adam is headtrain.hip's kernel.
-#include "host.h"
+// Host side of the attention layer's training step (include/sdfa_attntrain.h): the layer's tensor table,
+// the workspace layout and the launches of attntrain.hip over the flat training state of trainstate.h.
 #include "attntrain.h"
-#include "headtrain.h"
+#include "trainstate.h"
 
 #include <string.h>
 
-#include <vector>
+#include <string>
 
 namespace {
 
+const char *const MOD = "attntrain";
+TS_SAME_BUFFERS(SDFA_ATTNTRAIN);
 constexpr int NT = 5;
 constexpr int64_t QW = (int64_t)AT_KW * AT_D;
 const char *const PREFIX = "_audio_encoder._layers.10.";
@@ -30,12 +31,7 @@ struct Ws {
 
 Ws ws_layout(int64_t N) {
     Ws w;
-    int64_t off = 0;
-    auto take = [&](int64_t floats) {
-        const int64_t at = off;
-        off += round_up(floats, 64);
-        return at;
-    };
+    WsTake take;
     w.nblk = (int)((N + AT_BLOCK_FRAMES - 1) / AT_BLOCK_FRAMES);
     w.qc = take(N * AT_D);
     w.qp = take(N * AT_A);
@@ -48,7 +44,7 @@ Ws ws_layout(int64_t N) {
     w.dHq = take(N * QW);
     w.part = take((int64_t)w.nblk * AT_A * AT_D);
     w.partv = take((int64_t)w.nblk * 2 * AT_A);
-    w.total = off * 4;
+    w.total = take.bytes();
     return w;
 }
 
@@ -56,19 +52,14 @@ Ws ws_layout(int64_t N) {
 
 struct sdfa_attntrain {
     int64_t off[NT + 1];
-    std::vector<float> host;             // the parameters until finalize
-    char have[NT];
-    bool finalized;
-    float *d_param, *d_grad, *d_m, *d_v;
-    int64_t step;
-    int64_t fwd_N;                       // frames of the last forward, 0 when there is none
-    const void *fwd_ws;
+    TrainState ts;                       // a slot per tensor
 };
 
 namespace {
 
-int locate(const sdfa_attntrain *h, const char *who, const char *name, int64_t numel) {
-    if (!h || !name) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
+// The slot of tensor `name`; `data` is the caller's host pointer, refused first.
+int locate(const sdfa_attntrain *h, const char *who, const char *name, const void *data, int64_t numel) {
+    if (!data || !h || !name) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
     const size_t np = strlen(PREFIX);
     int ti = -1;
     if (strncmp(name, PREFIX, np) == 0)
@@ -80,20 +71,11 @@ int locate(const sdfa_attntrain *h, const char *who, const char *name, int64_t n
     return ti;
 }
 
-float *buffer_of(sdfa_attntrain *h, int what) {
-    return what == SDFA_ATTNTRAIN_PARAM ? h->d_param : what == SDFA_ATTNTRAIN_GRAD ? h->d_grad : what == SDFA_ATTNTRAIN_EXP_AVG ? h->d_m
-         : what == SDFA_ATTNTRAIN_EXP_AVG_SQ ? h->d_v : nullptr;
-}
-
-int check_call(const sdfa_attntrain *h, const char *who, int64_t N, const void *d_ws, int64_t ws_bytes) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "%s: null handle", who);
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "%s: the handle is not finalised", who);
-    if (N < 1 || N > SDFA_ATTNTRAIN_MAX_FRAMES) return sdfa_fail(SDFA_EINVAL, "%s: %lld frames outside 1 .. %d", who, (long long)N, SDFA_ATTNTRAIN_MAX_FRAMES);
-    if (!d_ws) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
-    const int64_t need = ws_layout(N).total;
-    if (ws_bytes < need) return sdfa_fail(SDFA_EINVAL, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes, (long long)need);
-    if ((uintptr_t)d_ws % 256 != 0) return sdfa_fail(SDFA_EINVAL, "%s: workspace not 256-byte aligned", who);
-    return SDFA_OK;
+int check_call(const sdfa_attntrain *h, const char *fn, int64_t N, const void *d_ws, int64_t ws_bytes) {
+    const int rc = ts_ready(ts_of(h), MOD, fn);
+    if (rc < 0) return rc;
+    if (N < 1 || N > SDFA_ATTNTRAIN_MAX_FRAMES) return sdfa_fail(SDFA_EINVAL, "attntrain_%s: %lld frames outside 1 .. %d", fn, (long long)N, SDFA_ATTNTRAIN_MAX_FRAMES);
+    return ts_check_ws(MOD, fn, d_ws, ws_bytes, ws_layout(N).total);
 }
 
 AtOp op(const float *p, int64_t si, int64_t sc, int64_t ni, int nc) { return AtOp{p, si, sc, ni, nc}; }
@@ -107,58 +89,28 @@ int sdfa_attntrain_abi_version(void) { return SDFA_ATTNTRAIN_ABI_VERSION; }
 sdfa_attntrain *sdfa_attntrain_create(void) {
     sdfa_attntrain *h = new sdfa_attntrain();
     h->off[0] = 0;
-    for (int i = 0; i < NT; ++i) {
-        h->off[i + 1] = h->off[i] + TENSOR[i].numel;
-        h->have[i] = 0;
-    }
-    h->host.assign((size_t)h->off[NT], 0.f);
-    h->finalized = false;
-    h->d_param = h->d_grad = h->d_m = h->d_v = nullptr;
-    h->step = 0;
-    h->fwd_N = 0;
-    h->fwd_ws = nullptr;
+    for (int i = 0; i < NT; ++i) h->off[i + 1] = h->off[i] + TENSOR[i].numel;
+    ts_init(h->ts, h->off[NT], NT);
     return h;
 }
 
 void sdfa_attntrain_destroy(sdfa_attntrain *h) {
     if (!h) return;
-    for (float *p : {h->d_param, h->d_grad, h->d_m, h->d_v})
-        if (p) (void)hipFree(p);
+    ts_free(h->ts);
     delete h;
 }
 
 int sdfa_attntrain_set_tensor(sdfa_attntrain *h, const char *name, const float *h_src, int64_t numel) {
-    if (!h_src) return sdfa_fail(SDFA_EINVAL, "attntrain_set_tensor: null pointer");
-    const int ti = locate(h, "attntrain_set_tensor", name, numel);
-    if (ti < 0) return ti;
-    if (h->finalized) return sdfa_fail(SDFA_ESTATE, "attntrain_set_tensor: the handle is finalised (sdfa_attntrain_set_state writes a parameter then)");
-    memcpy(h->host.data() + h->off[ti], h_src, (size_t)numel * sizeof(float));
-    h->have[ti] = 1;
-    return SDFA_OK;
+    const int ti = locate(h, "attntrain_set_tensor", name, h_src, numel);
+    return ti < 0 ? ti : ts_set_tensor(h->ts, MOD, ti, h->off[ti], h_src, numel);
 }
 
 int sdfa_attntrain_finalize(sdfa_attntrain *h, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "attntrain_finalize: null handle");
-    if (h->finalized) return sdfa_fail(SDFA_ESTATE, "attntrain_finalize: already finalised");
-    for (int i = 0; i < NT; ++i)
-        if (!h->have[i]) return sdfa_fail(SDFA_ESTATE, "attntrain_finalize: tensor \"%s%s\" is missing", PREFIX, TENSOR[i].name);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nb = (size_t)h->off[NT] * sizeof(float);
-    HIP_TRY(hipMalloc((void **)&h->d_param, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_grad, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_m, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_v, nb));
-    HIP_TRY(hipMemcpyAsync(h->d_param, h->host.data(), nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_grad, 0, nb, st));
-    HIP_TRY(hipMemsetAsync(h->d_m, 0, nb, st));
-    HIP_TRY(hipMemsetAsync(h->d_v, 0, nb, st));
-    HIP_TRY(hipStreamSynchronize(st));             // the host copy is released below
-    std::vector<float>().swap(h->host);
-    h->finalized = true;
-    return SDFA_OK;
+    const int rc = ts_check_finalize(ts_of(h), MOD, [](int ti) { return std::string(PREFIX) + TENSOR[ti].name; });
+    return rc < 0 ? rc : ts_finalize(h->ts, (hipStream_t)stream);
 }
 
-int64_t sdfa_attntrain_numel(const sdfa_attntrain *h) { return h ? h->off[NT] : sdfa_fail(SDFA_EINVAL, "attntrain_numel: null handle"); }
+int64_t sdfa_attntrain_numel(const sdfa_attntrain *h) { return ts_numel(ts_of(h), MOD); }
 
 int64_t sdfa_attntrain_workspace_bytes(const sdfa_attntrain *h, int64_t max_frames) {
     if (!h) return sdfa_fail(SDFA_EINVAL, "attntrain_workspace_bytes: null handle");
@@ -169,14 +121,14 @@ int64_t sdfa_attntrain_workspace_bytes(const sdfa_attntrain *h, int64_t max_fram
 
 int sdfa_attntrain_forward(sdfa_attntrain *h, const float *d_H, int64_t N, float *d_z, float *d_align, void *d_ws, int64_t ws_bytes,
                            void *stream) {
-    const int rc = check_call(h, "attntrain_forward", N, d_ws, ws_bytes);
+    const int rc = check_call(h, "forward", N, d_ws, ws_bytes);
     if (rc < 0) return rc;
     if (!d_H || !d_z || !d_align) return sdfa_fail(SDFA_EINVAL, "attntrain_forward: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const Ws w = ws_layout(N);
     float *f = (float *)d_ws;
-    const float *P = h->d_param;
-    h->fwd_N = 0;                                           // a forward that fails half way is no forward
+    const float *P = h->ts.d_param;
+    h->ts.fwd_N = 0;                                        // a forward that fails half way is no forward
     AtProdArgs p;
     p.A = op(d_H + AT_W0 * AT_D, (int64_t)AT_T * AT_D, 1, N, (int)QW);      // the window H[n][31 .. 33][:], contiguous
     p.B = op(P + h->off[WC], QW, 1, AT_D, (int)QW);
@@ -200,22 +152,22 @@ int sdfa_attntrain_forward(sdfa_attntrain *h, const float *d_H, int64_t N, float
     a.align = d_align;
     a.N = N;
     HIP_TRY(attntrain_frame_forward(a, st));
-    h->fwd_N = N;
-    h->fwd_ws = d_ws;
+    h->ts.fwd_N = N;
+    h->ts.fwd_ws = d_ws;
     return SDFA_OK;
 }
 
 int sdfa_attntrain_backward(sdfa_attntrain *h, const float *d_H, const float *d_dz, int64_t N, float *d_dH, void *d_ws,
                             int64_t ws_bytes, void *stream) {
-    const int rc = check_call(h, "attntrain_backward", N, d_ws, ws_bytes);
+    const int rc = check_call(h, "backward", N, d_ws, ws_bytes);
     if (rc < 0) return rc;
     if (!d_H || !d_dz) return sdfa_fail(SDFA_EINVAL, "attntrain_backward: null pointer");
-    if (h->fwd_N != N || h->fwd_ws != d_ws)
-        return sdfa_fail(SDFA_EINVAL, "attntrain_backward: no forward of %lld frames on this workspace precedes it", (long long)N);
+    const int rf = ts_check_forward(h->ts, MOD, N, d_ws, "frames");
+    if (rf < 0) return rf;
     hipStream_t st = (hipStream_t)stream;
     const Ws w = ws_layout(N);
     float *f = (float *)d_ws;
-    const float *P = h->d_param;
+    const float *P = h->ts.d_param;
     AtFrameBwdArgs fb;
     fb.H = d_H;
     fb.dz = d_dz;
@@ -251,8 +203,8 @@ int sdfa_attntrain_backward(sdfa_attntrain *h, const float *d_H, const float *d_
     b.qc = f + w.qc;
     b.dHq = f + w.dHq;
     b.Wk = P + h->off[WK];
-    b.gWc = h->d_grad + h->off[WC];
-    b.gWq = h->d_grad + h->off[WQ];
+    b.gWc = h->ts.d_grad + h->off[WC];
+    b.gWq = h->ts.d_grad + h->off[WQ];
     b.part = f + w.part;
     b.partv = f + w.partv;
     b.dH = d_dH;
@@ -262,69 +214,35 @@ int sdfa_attntrain_backward(sdfa_attntrain *h, const float *d_H, const float *d_
     AtReduceArgs r;
     r.part = f + w.part;
     r.partv = f + w.partv;
-    r.gWk = h->d_grad + h->off[WK];
-    r.gv = h->d_grad + h->off[V];
-    r.gb = h->d_grad + h->off[B];
+    r.gWk = h->ts.d_grad + h->off[WK];
+    r.gv = h->ts.d_grad + h->off[V];
+    r.gb = h->ts.d_grad + h->off[B];
     r.nblk = w.nblk;
     HIP_TRY(attntrain_reduce(r, st));
     return SDFA_OK;
 }
 
 int sdfa_attntrain_adam(sdfa_attntrain *h, double lr, double beta1, double beta2, double eps, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "attntrain_adam: null handle");
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "attntrain_adam: the handle is not finalised");
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return sdfa_fail(SDFA_EINVAL, "attntrain_adam: lr %g, betas (%g, %g), eps %g: torch.optim.Adam refuses these", lr, beta1, beta2, eps);
-    const int64_t t = h->step + 1;
-    HIP_TRY(headtrain_adam_step(h->d_param, h->d_grad, h->d_m, h->d_v, h->off[NT], t, lr, beta1, beta2, eps, (hipStream_t)stream));
-    h->step = t;
-    h->fwd_N = 0;                                           // the kept activations belong to the old parameters
-    return SDFA_OK;
+    return ts_adam(ts_of(h), MOD, lr, beta1, beta2, eps, stream);
 }
 
-int sdfa_attntrain_zero_grad(sdfa_attntrain *h, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "attntrain_zero_grad: null handle");
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "attntrain_zero_grad: the handle is not finalised");
-    HIP_TRY(hipMemsetAsync(h->d_grad, 0, (size_t)h->off[NT] * sizeof(float), (hipStream_t)stream));
-    return SDFA_OK;
-}
+int sdfa_attntrain_zero_grad(sdfa_attntrain *h, void *stream) { return ts_zero_grad(ts_of(h), MOD, stream); }
 
 int sdfa_attntrain_get_tensor(sdfa_attntrain *h, const char *name, int what, float *h_dst, int64_t numel) {
-    if (!h_dst) return sdfa_fail(SDFA_EINVAL, "attntrain_get_tensor: null pointer");
-    const int ti = locate(h, "attntrain_get_tensor", name, numel);
-    if (ti < 0) return ti;
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "attntrain_get_tensor: the handle is not finalised");
-    const float *src = buffer_of(h, what);
-    if (!src) return sdfa_fail(SDFA_EINVAL, "attntrain_get_tensor: unknown buffer %d", what);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h_dst, src + h->off[ti], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-    return SDFA_OK;
+    const int ti = locate(h, "attntrain_get_tensor", name, h_dst, numel);
+    return ti < 0 ? ti : ts_get_tensor(h->ts, MOD, what, h->off[ti], h_dst, numel);
 }
 
 int sdfa_attntrain_set_state(sdfa_attntrain *h, const char *name, int what, const float *h_src, int64_t numel) {
-    if (!h_src) return sdfa_fail(SDFA_EINVAL, "attntrain_set_state: null pointer");
-    const int ti = locate(h, "attntrain_set_state", name, numel);
-    if (ti < 0) return ti;
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "attntrain_set_state: the handle is not finalised");
-    float *dst = buffer_of(h, what);
-    if (!dst) return sdfa_fail(SDFA_EINVAL, "attntrain_set_state: unknown buffer %d", what);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(dst + h->off[ti], h_src, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    if (what == SDFA_ATTNTRAIN_PARAM) h->fwd_N = 0;
-    return SDFA_OK;
+    const int ti = locate(h, "attntrain_set_state", name, h_src, numel);
+    return ti < 0 ? ti : ts_set_state(h->ts, MOD, what, h->off[ti], h_src, numel);
 }
 
 int sdfa_attntrain_set_grad(sdfa_attntrain *h, const char *name, const float *h_src, int64_t numel) {
     return sdfa_attntrain_set_state(h, name, SDFA_ATTNTRAIN_GRAD, h_src, numel);
 }
 
-int64_t sdfa_attntrain_step_count(const sdfa_attntrain *h) { return h ? h->step : sdfa_fail(SDFA_EINVAL, "attntrain_step_count: null handle"); }
-
-int sdfa_attntrain_set_step_count(sdfa_attntrain *h, int64_t t) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "attntrain_set_step_count: null handle");
-    if (t < 0) return sdfa_fail(SDFA_EINVAL, "attntrain_set_step_count: %lld is negative", (long long)t);
-    h->step = t;
-    return SDFA_OK;
-}
+int64_t sdfa_attntrain_step_count(const sdfa_attntrain *h) { return ts_step_count(ts_of(h), MOD); }
+int sdfa_attntrain_set_step_count(sdfa_attntrain *h, int64_t t) { return ts_set_step_count(ts_of(h), MOD, t); }
 
 }  // extern "C"

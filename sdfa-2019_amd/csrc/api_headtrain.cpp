@@ -1,13 +1,10 @@
-// Host side of the regressor head's training step (include/sdfa_headtrain.h): the handle and its flat
-// device buffers, the refusals, the workspace layout and the launches of headtrain.hip.
-#include "host.h"
+// Host side of the regressor head's training step (include/sdfa_headtrain.h): the head's tensor table, its
+// effective-weight buffers, the workspace layout and the launches of headtrain.hip over the flat training state of trainstate.h.
 #include "headtrain.h"
 
-#include <math.h>
 #include <string.h>
 
 #include <string>
-#include <vector>
 
 namespace {
 
@@ -38,32 +35,26 @@ struct Ws {
     int64_t z, sid, h0, h1[2], h2[2], d2[2], d1[2], d0, total;
 };
 
+const char *const MOD = "headtrain";
+const char *const SUF[3] = {".weight_g", ".weight_v", ".bias"};
+TS_SAME_BUFFERS(SDFA_HEADTRAIN);
+
 }  // namespace
 
 struct sdfa_headtrain {
     int head, nb, kc;
     const Spec *spec;
     HtTable t;
-    int64_t numel, wnumel;               // floats of a parameter-shaped buffer; of W
-    std::vector<float> host;             // the parameters until finalize
-    std::vector<char> have;              // [layer][g, v, bias]
-    bool finalized;
-    float *d_param, *d_grad, *d_m, *d_v, *d_W, *d_dW, *d_inv, *d_sc;
-    int64_t step;
-    int64_t fwd_N;                       // rows of the last forward, 0 when there is none
-    const void *fwd_ws;
+    int64_t wnumel;                      // floats of W
+    TrainState ts;                       // slots [layer][g, v, bias]
+    float *d_W, *d_dW, *d_inv, *d_sc;
 };
 
 namespace {
 
 Ws ws_layout(const sdfa_headtrain *h, int64_t N) {
     Ws w;
-    int64_t off = 0;
-    auto take = [&](int64_t floats) {
-        const int64_t at = off;
-        off += round_up(floats, 64);
-        return at;
-    };
+    WsTake take;
     w.z = take(N * SDFA_HEADTRAIN_Z);
     w.sid = take(N);
     w.h0 = w.d0 = 0;
@@ -78,13 +69,12 @@ Ws ws_layout(const sdfa_headtrain *h, int64_t N) {
         w.d2[b] = on ? take(N * 256) : 0;
         w.d1[b] = on ? take(N * 512) : 0;
     }
-    w.total = off * 4;
+    w.total = take.bytes();
     return w;
 }
 
 // name -> (layer, part 0 g | 1 v | 2 bias); -1 when the head has no such tensor
 int find_tensor(const sdfa_headtrain *h, const char *name, int *part) {
-    static const char *const SUF[3] = {".weight_g", ".weight_v", ".bias"};
     for (int li = 0; li < h->t.nl; ++li) {
         const size_t n = strlen(h->spec[li].name);
         if (strncmp(name, h->spec[li].name, n) != 0) continue;
@@ -100,8 +90,9 @@ int find_tensor(const sdfa_headtrain *h, const char *name, int *part) {
 int64_t part_offset(const HtLayer &L, int part) { return part == 0 ? L.og : part == 1 ? L.ov : L.ob; }
 int64_t part_numel(const HtLayer &L, int part) { return part == 1 ? (int64_t)L.P * L.K : L.P; }
 
-int locate(const sdfa_headtrain *h, const char *who, const char *name, int64_t numel, int64_t *off) {
-    if (!h || !name) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
+// The slot of tensor `name` and its offset in a parameter-shaped buffer; `data` is the caller's host pointer, refused first.
+int locate(const sdfa_headtrain *h, const char *who, const char *name, const void *data, int64_t numel, int64_t *off) {
+    if (!data || !h || !name) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
     int part = 0;
     const int li = find_tensor(h, name, &part);
     if (li < 0) return sdfa_fail(SDFA_EINVAL, "%s: the head has no tensor \"%s\"", who, name);
@@ -111,21 +102,12 @@ int locate(const sdfa_headtrain *h, const char *who, const char *name, int64_t n
     return li * 3 + part;
 }
 
-float *buffer_of(sdfa_headtrain *h, int what) {
-    return what == SDFA_HEADTRAIN_PARAM ? h->d_param : what == SDFA_HEADTRAIN_GRAD ? h->d_grad : what == SDFA_HEADTRAIN_EXP_AVG ? h->d_m
-         : what == SDFA_HEADTRAIN_EXP_AVG_SQ ? h->d_v : nullptr;
-}
-
-int check_call(const sdfa_headtrain *h, const char *who, int64_t N, const void *d_ws, int64_t ws_bytes) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "%s: null handle", who);
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "%s: the handle is not finalised", who);
-    if (N < 2 || N % 2 != 0) return sdfa_fail(SDFA_EINVAL, "%s: a batch of %lld rows is not [a; b] with at least one pair", who, (long long)N);
-    if (N > SDFA_HEADTRAIN_MAX_ROWS) return sdfa_fail(SDFA_EINVAL, "%s: %lld rows, at most %d", who, (long long)N, SDFA_HEADTRAIN_MAX_ROWS);
-    if (!d_ws) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
-    const int64_t need = ws_layout(h, N).total;
-    if (ws_bytes < need) return sdfa_fail(SDFA_EINVAL, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes, (long long)need);
-    if ((uintptr_t)d_ws % 256 != 0) return sdfa_fail(SDFA_EINVAL, "%s: workspace not 256-byte aligned", who);
-    return SDFA_OK;
+int check_call(const sdfa_headtrain *h, const char *fn, int64_t N, const void *d_ws, int64_t ws_bytes) {
+    const int rc = ts_ready(ts_of(h), MOD, fn);
+    if (rc < 0) return rc;
+    if (N < 2 || N % 2 != 0) return sdfa_fail(SDFA_EINVAL, "headtrain_%s: a batch of %lld rows is not [a; b] with at least one pair", fn, (long long)N);
+    if (N > SDFA_HEADTRAIN_MAX_ROWS) return sdfa_fail(SDFA_EINVAL, "headtrain_%s: %lld rows, at most %d", fn, (long long)N, SDFA_HEADTRAIN_MAX_ROWS);
+    return ts_check_ws(MOD, fn, d_ws, ws_bytes, ws_layout(h, N).total);
 }
 
 HtFwdJob fwd_job(const sdfa_headtrain *h, int li, const float *X, int ldx, float *Y, int ldy) {
@@ -133,7 +115,7 @@ HtFwdJob fwd_job(const sdfa_headtrain *h, int li, const float *X, int ldx, float
     HtFwdJob j;
     j.X = X;
     j.W = h->d_W + L.ow;
-    j.bias = h->d_param + L.ob;
+    j.bias = h->ts.d_param + L.ob;
     j.Y = Y;
     j.ldx = ldx;
     j.ldw = L.K;
@@ -152,7 +134,7 @@ HtBwdJob bwd_job(const sdfa_headtrain *h, int li, const float *D, int ldd, const
     j.X = X;
     j.W = h->d_W + L.ow;
     j.dW = h->d_dW + L.ow;
-    j.db = h->d_grad + L.ob;
+    j.db = h->ts.d_grad + L.ob;
     j.Yprev = Yprev;
     j.Dprev = Dprev;
     j.ldd = ldd;
@@ -206,65 +188,41 @@ sdfa_headtrain *sdfa_headtrain_create(int head) {
         row += s.P;
     }
     h->t.rows = row;
-    h->numel = off;
     h->wnumel = woff;
-    h->host.assign((size_t)off, 0.f);
-    h->have.assign((size_t)h->t.nl * 3, 0);
-    h->finalized = false;
-    h->d_param = h->d_grad = h->d_m = h->d_v = h->d_W = h->d_dW = h->d_inv = h->d_sc = nullptr;
-    h->step = 0;
-    h->fwd_N = 0;
-    h->fwd_ws = nullptr;
+    ts_init(h->ts, off, (size_t)h->t.nl * 3);
+    h->d_W = h->d_dW = h->d_inv = h->d_sc = nullptr;
     return h;
 }
 
 void sdfa_headtrain_destroy(sdfa_headtrain *h) {
     if (!h) return;
-    for (float *p : {h->d_param, h->d_grad, h->d_m, h->d_v, h->d_W, h->d_dW, h->d_inv, h->d_sc})
+    ts_free(h->ts);
+    for (float *p : {h->d_W, h->d_dW, h->d_inv, h->d_sc})
         if (p) (void)hipFree(p);
     delete h;
 }
 
 int sdfa_headtrain_set_tensor(sdfa_headtrain *h, const char *name, const float *h_src, int64_t numel) {
-    if (!h_src) return sdfa_fail(SDFA_EINVAL, "headtrain_set_tensor: null pointer");
     int64_t off = 0;
-    const int slot = locate(h, "headtrain_set_tensor", name, numel, &off);
-    if (slot < 0) return slot;
-    if (h->finalized) return sdfa_fail(SDFA_ESTATE, "headtrain_set_tensor: the handle is finalised (sdfa_headtrain_set_state writes a parameter then)");
-    memcpy(h->host.data() + off, h_src, (size_t)numel * sizeof(float));
-    h->have[slot] = 1;
-    return SDFA_OK;
+    const int slot = locate(h, "headtrain_set_tensor", name, h_src, numel, &off);
+    return slot < 0 ? slot : ts_set_tensor(h->ts, MOD, slot, off, h_src, numel);
 }
 
 int sdfa_headtrain_finalize(sdfa_headtrain *h, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "headtrain_finalize: null handle");
-    if (h->finalized) return sdfa_fail(SDFA_ESTATE, "headtrain_finalize: already finalised");
-    static const char *const SUF[3] = {".weight_g", ".weight_v", ".bias"};
-    for (size_t s = 0; s < h->have.size(); ++s)
-        if (!h->have[s]) return sdfa_fail(SDFA_ESTATE, "headtrain_finalize: tensor \"%s%s\" is missing", h->spec[s / 3].name, SUF[s % 3]);
+    const int rc = ts_check_finalize(ts_of(h), MOD, [&](int slot) { return std::string(h->spec[slot / 3].name) + SUF[slot % 3]; });
+    if (rc < 0) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t nb = (size_t)h->numel * sizeof(float), wb = (size_t)h->wnumel * sizeof(float), rb = (size_t)h->t.rows * sizeof(float);
-    HIP_TRY(hipMalloc((void **)&h->d_param, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_grad, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_m, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_v, nb));
+    const size_t wb = (size_t)h->wnumel * sizeof(float), rb = (size_t)h->t.rows * sizeof(float);
     HIP_TRY(hipMalloc((void **)&h->d_W, wb));
     HIP_TRY(hipMalloc((void **)&h->d_dW, wb));
     HIP_TRY(hipMalloc((void **)&h->d_inv, rb));
     HIP_TRY(hipMalloc((void **)&h->d_sc, rb));
-    HIP_TRY(hipMemcpyAsync(h->d_param, h->host.data(), nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_grad, 0, nb, st));
-    HIP_TRY(hipMemsetAsync(h->d_m, 0, nb, st));
-    HIP_TRY(hipMemsetAsync(h->d_v, 0, nb, st));
     HIP_TRY(hipMemsetAsync(h->d_dW, 0, wb, st));
-    HIP_TRY(hipStreamSynchronize(st));             // the host copy is released below
-    std::vector<float>().swap(h->host);
-    h->finalized = true;
-    return SDFA_OK;
+    return ts_finalize(h->ts, st);
 }
 
 int sdfa_headtrain_coef_dim(const sdfa_headtrain *h) { return h ? h->kc : sdfa_fail(SDFA_EINVAL, "headtrain_coef_dim: null handle"); }
-int64_t sdfa_headtrain_numel(const sdfa_headtrain *h) { return h ? h->numel : sdfa_fail(SDFA_EINVAL, "headtrain_numel: null handle"); }
+int64_t sdfa_headtrain_numel(const sdfa_headtrain *h) { return ts_numel(ts_of(h), MOD); }
 
 int64_t sdfa_headtrain_workspace_bytes(const sdfa_headtrain *h, int64_t max_rows) {
     if (!h) return sdfa_fail(SDFA_EINVAL, "headtrain_workspace_bytes: null handle");
@@ -274,14 +232,14 @@ int64_t sdfa_headtrain_workspace_bytes(const sdfa_headtrain *h, int64_t max_rows
 
 int sdfa_headtrain_forward(sdfa_headtrain *h, const float *d_z, const int64_t *d_speaker_id, int64_t N, float *d_coef,
                            void *d_ws, int64_t ws_bytes, void *stream) {
-    const int rc = check_call(h, "headtrain_forward", N, d_ws, ws_bytes);
+    const int rc = check_call(h, "forward", N, d_ws, ws_bytes);
     if (rc < 0) return rc;
     if (!d_z || !d_speaker_id || !d_coef) return sdfa_fail(SDFA_EINVAL, "headtrain_forward: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const Ws w = ws_layout(h, N);
     float *f = (float *)d_ws;
-    h->fwd_N = 0;                                           // a forward that fails half way is no forward
-    HIP_TRY(headtrain_fold(h->t, h->d_param, h->d_W, h->d_inv, h->d_sc, st));
+    h->ts.fwd_N = 0;                                        // a forward that fails half way is no forward
+    HIP_TRY(headtrain_fold(h->t, h->ts.d_param, h->d_W, h->d_inv, h->d_sc, st));
     HtFwdArgs a;
     a.N = N;
     a.sid = d_speaker_id;
@@ -314,17 +272,17 @@ int sdfa_headtrain_forward(sdfa_headtrain *h, const float *d_z, const int64_t *d
         a.zcopy = nullptr;
         a.sidcopy = nullptr;
     }
-    h->fwd_N = N;
-    h->fwd_ws = d_ws;
+    h->ts.fwd_N = N;
+    h->ts.fwd_ws = d_ws;
     return SDFA_OK;
 }
 
 int sdfa_headtrain_backward(sdfa_headtrain *h, const float *d_dcoef, int64_t N, float *d_dz, void *d_ws, int64_t ws_bytes, void *stream) {
-    const int rc = check_call(h, "headtrain_backward", N, d_ws, ws_bytes);
+    const int rc = check_call(h, "backward", N, d_ws, ws_bytes);
     if (rc < 0) return rc;
     if (!d_dcoef) return sdfa_fail(SDFA_EINVAL, "headtrain_backward: null pointer");
-    if (h->fwd_N != N || h->fwd_ws != d_ws)
-        return sdfa_fail(SDFA_EINVAL, "headtrain_backward: no forward of %lld rows on this workspace precedes it", (long long)N);
+    const int rf = ts_check_forward(h->ts, MOD, N, d_ws, "rows");
+    if (rf < 0) return rf;
     hipStream_t st = (hipStream_t)stream;
     const Ws w = ws_layout(h, N);
     float *f = (float *)d_ws;
@@ -370,67 +328,33 @@ int sdfa_headtrain_backward(sdfa_headtrain *h, const float *d_dcoef, int64_t N, 
         a.act_prev = HT_ACT_LINEAR;
         HIP_TRY(headtrain_backward_layer(a, st));
     }
-    HIP_TRY(headtrain_wnorm_backward(h->t, h->d_param, h->d_dW, h->d_inv, h->d_sc, h->d_grad, st));
+    HIP_TRY(headtrain_wnorm_backward(h->t, h->ts.d_param, h->d_dW, h->d_inv, h->d_sc, h->ts.d_grad, st));
     return SDFA_OK;
 }
 
 int sdfa_headtrain_adam(sdfa_headtrain *h, double lr, double beta1, double beta2, double eps, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "headtrain_adam: null handle");
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "headtrain_adam: the handle is not finalised");
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return sdfa_fail(SDFA_EINVAL, "headtrain_adam: lr %g, betas (%g, %g), eps %g: torch.optim.Adam refuses these", lr, beta1, beta2, eps);
-    const int64_t t = h->step + 1;
-    HIP_TRY(headtrain_adam_step(h->d_param, h->d_grad, h->d_m, h->d_v, h->numel, t, lr, beta1, beta2, eps, (hipStream_t)stream));
-    h->step = t;
-    h->fwd_N = 0;                                           // the kept activations belong to the old parameters
-    return SDFA_OK;
+    return ts_adam(ts_of(h), MOD, lr, beta1, beta2, eps, stream);
 }
 
-int sdfa_headtrain_zero_grad(sdfa_headtrain *h, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "headtrain_zero_grad: null handle");
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "headtrain_zero_grad: the handle is not finalised");
-    HIP_TRY(hipMemsetAsync(h->d_grad, 0, (size_t)h->numel * sizeof(float), (hipStream_t)stream));
-    return SDFA_OK;
-}
+int sdfa_headtrain_zero_grad(sdfa_headtrain *h, void *stream) { return ts_zero_grad(ts_of(h), MOD, stream); }
 
 int sdfa_headtrain_get_tensor(sdfa_headtrain *h, const char *name, int what, float *h_dst, int64_t numel) {
-    if (!h_dst) return sdfa_fail(SDFA_EINVAL, "headtrain_get_tensor: null pointer");
     int64_t off = 0;
-    const int slot = locate(h, "headtrain_get_tensor", name, numel, &off);
-    if (slot < 0) return slot;
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "headtrain_get_tensor: the handle is not finalised");
-    const float *src = buffer_of(h, what);
-    if (!src) return sdfa_fail(SDFA_EINVAL, "headtrain_get_tensor: unknown buffer %d", what);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h_dst, src + off, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-    return SDFA_OK;
+    const int slot = locate(h, "headtrain_get_tensor", name, h_dst, numel, &off);
+    return slot < 0 ? slot : ts_get_tensor(h->ts, MOD, what, off, h_dst, numel);
 }
 
 int sdfa_headtrain_set_state(sdfa_headtrain *h, const char *name, int what, const float *h_src, int64_t numel) {
-    if (!h_src) return sdfa_fail(SDFA_EINVAL, "headtrain_set_state: null pointer");
     int64_t off = 0;
-    const int slot = locate(h, "headtrain_set_state", name, numel, &off);
-    if (slot < 0) return slot;
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "headtrain_set_state: the handle is not finalised");
-    float *dst = buffer_of(h, what);
-    if (!dst) return sdfa_fail(SDFA_EINVAL, "headtrain_set_state: unknown buffer %d", what);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(dst + off, h_src, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    if (what == SDFA_HEADTRAIN_PARAM) h->fwd_N = 0;
-    return SDFA_OK;
+    const int slot = locate(h, "headtrain_set_state", name, h_src, numel, &off);
+    return slot < 0 ? slot : ts_set_state(h->ts, MOD, what, off, h_src, numel);
 }
 
 int sdfa_headtrain_set_grad(sdfa_headtrain *h, const char *name, const float *h_src, int64_t numel) {
     return sdfa_headtrain_set_state(h, name, SDFA_HEADTRAIN_GRAD, h_src, numel);
 }
 
-int64_t sdfa_headtrain_step_count(const sdfa_headtrain *h) { return h ? h->step : sdfa_fail(SDFA_EINVAL, "headtrain_step_count: null handle"); }
-
-int sdfa_headtrain_set_step_count(sdfa_headtrain *h, int64_t t) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "headtrain_set_step_count: null handle");
-    if (t < 0) return sdfa_fail(SDFA_EINVAL, "headtrain_set_step_count: %lld is negative", (long long)t);
-    h->step = t;
-    return SDFA_OK;
-}
+int64_t sdfa_headtrain_step_count(const sdfa_headtrain *h) { return ts_step_count(ts_of(h), MOD); }
+int sdfa_headtrain_set_step_count(sdfa_headtrain *h, int64_t t) { return ts_set_step_count(ts_of(h), MOD, t); }
 
 }  // extern "C"

@@ -1,16 +1,17 @@
-// Host side of a bidirectional LSTM layer's training step (include/sdfa_lstmtrain.h): the handle and its
-// flat device buffers, the refusals, the workspace layout and the launches of lstmtrain.hip.  Adam is headtrain.hip's kernel.
-#include "host.h"
+// Host side of a bidirectional LSTM layer's training step (include/sdfa_lstmtrain.h): the layer's tensor
+// names, the workspace layout and the launches of lstmtrain.hip over the flat training state of trainstate.h.
 #include "lstmtrain.h"
-#include "headtrain.h"
+#include "trainstate.h"
 
 #include <stdio.h>
 #include <string.h>
 
-#include <vector>
+#include <string>
 
 namespace {
 
+const char *const MOD = "lstmtrain";
+TS_SAME_BUFFERS(SDFA_LSTMTRAIN);
 constexpr int NT = 4;
 const char *const PREFIX = "_audio_encoder._layers.9.";
 const char *const STEM[NT] = {"weight_ih_l%d", "weight_ih_l%d_reverse", "weight_hh_l%d", "weight_hh_l%d_reverse"};
@@ -24,19 +25,14 @@ struct Ws {
 
 Ws ws_layout(int64_t N, int64_t numel) {
     Ws w;
-    int64_t off = 0;
-    auto take = [&](int64_t floats) {
-        const int64_t at = off;
-        off += round_up(floats, 64);
-        return at;
-    };
+    WsTake take;
     w.nblk = (int)((N + LT_BLOCK_FRAMES - 1) / LT_BLOCK_FRAMES);
     w.gates = take(2 * N * LT_T * LT_G);
     w.c = take(2 * N * LT_T * LT_H);
     w.img = take(LT_IMG);
     w.imgT = take(LT_IMG);
     w.part = take((int64_t)w.nblk * numel);
-    w.total = off * 4;
+    w.total = take.bytes();
     return w;
 }
 
@@ -46,19 +42,14 @@ struct sdfa_lstmtrain {
     int in_dim, layer;
     char name[NT][64];                   // without PREFIX
     int64_t off[NT + 1];
-    std::vector<float> host;             // the parameters until finalize
-    char have[NT];
-    bool finalized;
-    float *d_param, *d_grad, *d_m, *d_v;
-    int64_t step;
-    int64_t fwd_N;                       // frames of the last forward, 0 when there is none
-    const void *fwd_ws;
+    TrainState ts;                       // a slot per tensor
 };
 
 namespace {
 
-int locate(const sdfa_lstmtrain *h, const char *who, const char *name, int64_t numel) {
-    if (!h || !name) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
+// The slot of tensor `name`; `data` is the caller's host pointer, refused first.
+int locate(const sdfa_lstmtrain *h, const char *who, const char *name, const void *data, int64_t numel) {
+    if (!data || !h || !name) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
     const size_t np = strlen(PREFIX);
     int ti = -1;
     if (strncmp(name, PREFIX, np) == 0)
@@ -70,20 +61,11 @@ int locate(const sdfa_lstmtrain *h, const char *who, const char *name, int64_t n
     return ti;
 }
 
-float *buffer_of(sdfa_lstmtrain *h, int what) {
-    return what == SDFA_LSTMTRAIN_PARAM ? h->d_param : what == SDFA_LSTMTRAIN_GRAD ? h->d_grad : what == SDFA_LSTMTRAIN_EXP_AVG ? h->d_m
-         : what == SDFA_LSTMTRAIN_EXP_AVG_SQ ? h->d_v : nullptr;
-}
-
-int check_call(const sdfa_lstmtrain *h, const char *who, int64_t N, const void *d_ws, int64_t ws_bytes) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "%s: null handle", who);
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "%s: the handle is not finalised", who);
-    if (N < 1 || N > SDFA_LSTMTRAIN_MAX_FRAMES) return sdfa_fail(SDFA_EINVAL, "%s: %lld frames outside 1 .. %d", who, (long long)N, SDFA_LSTMTRAIN_MAX_FRAMES);
-    if (!d_ws) return sdfa_fail(SDFA_EINVAL, "%s: null pointer", who);
-    const int64_t need = ws_layout(N, h->off[NT]).total;
-    if (ws_bytes < need) return sdfa_fail(SDFA_EINVAL, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes, (long long)need);
-    if ((uintptr_t)d_ws % 256 != 0) return sdfa_fail(SDFA_EINVAL, "%s: workspace not 256-byte aligned", who);
-    return SDFA_OK;
+int check_call(const sdfa_lstmtrain *h, const char *fn, int64_t N, const void *d_ws, int64_t ws_bytes) {
+    const int rc = ts_ready(ts_of(h), MOD, fn);
+    if (rc < 0) return rc;
+    if (N < 1 || N > SDFA_LSTMTRAIN_MAX_FRAMES) return sdfa_fail(SDFA_EINVAL, "lstmtrain_%s: %lld frames outside 1 .. %d", fn, (long long)N, SDFA_LSTMTRAIN_MAX_FRAMES);
+    return ts_check_ws(MOD, fn, d_ws, ws_bytes, ws_layout(N, h->off[NT]).total);
 }
 
 }  // namespace
@@ -104,56 +86,28 @@ sdfa_lstmtrain *sdfa_lstmtrain_create(int in_dim) {
     for (int i = 0; i < NT; ++i) {
         snprintf(h->name[i], sizeof h->name[i], STEM[i], h->layer);
         h->off[i + 1] = h->off[i] + (int64_t)LT_G * (i < WHH ? in_dim : LT_H);
-        h->have[i] = 0;
     }
-    h->host.assign((size_t)h->off[NT], 0.f);
-    h->finalized = false;
-    h->d_param = h->d_grad = h->d_m = h->d_v = nullptr;
-    h->step = 0;
-    h->fwd_N = 0;
-    h->fwd_ws = nullptr;
+    ts_init(h->ts, h->off[NT], NT);
     return h;
 }
 
 void sdfa_lstmtrain_destroy(sdfa_lstmtrain *h) {
     if (!h) return;
-    for (float *p : {h->d_param, h->d_grad, h->d_m, h->d_v})
-        if (p) (void)hipFree(p);
+    ts_free(h->ts);
     delete h;
 }
 
 int sdfa_lstmtrain_set_tensor(sdfa_lstmtrain *h, const char *name, const float *h_src, int64_t numel) {
-    if (!h_src) return sdfa_fail(SDFA_EINVAL, "lstmtrain_set_tensor: null pointer");
-    const int ti = locate(h, "lstmtrain_set_tensor", name, numel);
-    if (ti < 0) return ti;
-    if (h->finalized) return sdfa_fail(SDFA_ESTATE, "lstmtrain_set_tensor: the handle is finalised (sdfa_lstmtrain_set_state writes a parameter then)");
-    memcpy(h->host.data() + h->off[ti], h_src, (size_t)numel * sizeof(float));
-    h->have[ti] = 1;
-    return SDFA_OK;
+    const int ti = locate(h, "lstmtrain_set_tensor", name, h_src, numel);
+    return ti < 0 ? ti : ts_set_tensor(h->ts, MOD, ti, h->off[ti], h_src, numel);
 }
 
 int sdfa_lstmtrain_finalize(sdfa_lstmtrain *h, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "lstmtrain_finalize: null handle");
-    if (h->finalized) return sdfa_fail(SDFA_ESTATE, "lstmtrain_finalize: already finalised");
-    for (int i = 0; i < NT; ++i)
-        if (!h->have[i]) return sdfa_fail(SDFA_ESTATE, "lstmtrain_finalize: tensor \"%s%s\" is missing", PREFIX, h->name[i]);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nb = (size_t)h->off[NT] * sizeof(float);
-    HIP_TRY(hipMalloc((void **)&h->d_param, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_grad, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_m, nb));
-    HIP_TRY(hipMalloc((void **)&h->d_v, nb));
-    HIP_TRY(hipMemcpyAsync(h->d_param, h->host.data(), nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_grad, 0, nb, st));
-    HIP_TRY(hipMemsetAsync(h->d_m, 0, nb, st));
-    HIP_TRY(hipMemsetAsync(h->d_v, 0, nb, st));
-    HIP_TRY(hipStreamSynchronize(st));             // the host copy is released below
-    std::vector<float>().swap(h->host);
-    h->finalized = true;
-    return SDFA_OK;
+    const int rc = ts_check_finalize(ts_of(h), MOD, [&](int ti) { return std::string(PREFIX) + h->name[ti]; });
+    return rc < 0 ? rc : ts_finalize(h->ts, (hipStream_t)stream);
 }
 
-int64_t sdfa_lstmtrain_numel(const sdfa_lstmtrain *h) { return h ? h->off[NT] : sdfa_fail(SDFA_EINVAL, "lstmtrain_numel: null handle"); }
+int64_t sdfa_lstmtrain_numel(const sdfa_lstmtrain *h) { return ts_numel(ts_of(h), MOD); }
 
 int64_t sdfa_lstmtrain_workspace_bytes(const sdfa_lstmtrain *h, int64_t max_frames) {
     if (!h) return sdfa_fail(SDFA_EINVAL, "lstmtrain_workspace_bytes: null handle");
@@ -163,14 +117,14 @@ int64_t sdfa_lstmtrain_workspace_bytes(const sdfa_lstmtrain *h, int64_t max_fram
 }
 
 int sdfa_lstmtrain_forward(sdfa_lstmtrain *h, const float *d_X, int64_t N, float *d_Y, void *d_ws, int64_t ws_bytes, void *stream) {
-    const int rc = check_call(h, "lstmtrain_forward", N, d_ws, ws_bytes);
+    const int rc = check_call(h, "forward", N, d_ws, ws_bytes);
     if (rc < 0) return rc;
     if (!d_X || !d_Y) return sdfa_fail(SDFA_EINVAL, "lstmtrain_forward: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const Ws w = ws_layout(N, h->off[NT]);
     float *f = (float *)d_ws;
-    const float *P = h->d_param;
-    h->fwd_N = 0;                                           // a forward that fails half way is no forward
+    const float *P = h->ts.d_param;
+    h->ts.fwd_N = 0;                                        // a forward that fails half way is no forward
     LtImagesArgs im;
     im.Whh = P + h->off[WHH];
     im.img = f + w.img;
@@ -190,22 +144,22 @@ int sdfa_lstmtrain_forward(sdfa_lstmtrain *h, const float *d_X, int64_t N, float
     a.Y = d_Y;
     a.N = N;
     HIP_TRY(lstmtrain_forward(a, st));
-    h->fwd_N = N;
-    h->fwd_ws = d_ws;
+    h->ts.fwd_N = N;
+    h->ts.fwd_ws = d_ws;
     return SDFA_OK;
 }
 
 int sdfa_lstmtrain_backward(sdfa_lstmtrain *h, const float *d_X, const float *d_Y, const float *d_dY, int64_t N, float *d_dX,
                             void *d_ws, int64_t ws_bytes, void *stream) {
-    const int rc = check_call(h, "lstmtrain_backward", N, d_ws, ws_bytes);
+    const int rc = check_call(h, "backward", N, d_ws, ws_bytes);
     if (rc < 0) return rc;
     if (!d_X || !d_Y || !d_dY) return sdfa_fail(SDFA_EINVAL, "lstmtrain_backward: null pointer");
-    if (h->fwd_N != N || h->fwd_ws != d_ws)
-        return sdfa_fail(SDFA_EINVAL, "lstmtrain_backward: no forward of %lld frames on this workspace precedes it", (long long)N);
+    const int rf = ts_check_forward(h->ts, MOD, N, d_ws, "frames");
+    if (rf < 0) return rf;
     hipStream_t st = (hipStream_t)stream;
     const Ws w = ws_layout(N, h->off[NT]);
     float *f = (float *)d_ws;
-    h->fwd_N = 0;                                           // the kept gates become dG: one backward per forward
+    h->ts.fwd_N = 0;                                        // the kept gates become dG: one backward per forward
     LtBwdArgs b;
     b.imgT = f + w.imgT;
     b.c = f + w.c;
@@ -217,7 +171,7 @@ int sdfa_lstmtrain_backward(sdfa_lstmtrain *h, const float *d_X, const float *d_
     p.X = d_X;
     p.Y = d_Y;
     p.gates = f + w.gates;
-    p.Wih = h->d_param + h->off[WIH];
+    p.Wih = h->ts.d_param + h->off[WIH];
     p.part = f + w.part;
     p.dX = d_dX;
     p.N = N;
@@ -226,7 +180,7 @@ int sdfa_lstmtrain_backward(sdfa_lstmtrain *h, const float *d_X, const float *d_
     HIP_TRY(lstmtrain_products(p, st));
     LtReduceArgs r;
     r.part = f + w.part;
-    r.grad = h->d_grad;
+    r.grad = h->ts.d_grad;
     r.numel = h->off[NT];
     r.nblk = w.nblk;
     HIP_TRY(lstmtrain_reduce(r, st));
@@ -234,60 +188,26 @@ int sdfa_lstmtrain_backward(sdfa_lstmtrain *h, const float *d_X, const float *d_
 }
 
 int sdfa_lstmtrain_adam(sdfa_lstmtrain *h, double lr, double beta1, double beta2, double eps, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "lstmtrain_adam: null handle");
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "lstmtrain_adam: the handle is not finalised");
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return sdfa_fail(SDFA_EINVAL, "lstmtrain_adam: lr %g, betas (%g, %g), eps %g: torch.optim.Adam refuses these", lr, beta1, beta2, eps);
-    const int64_t t = h->step + 1;
-    HIP_TRY(headtrain_adam_step(h->d_param, h->d_grad, h->d_m, h->d_v, h->off[NT], t, lr, beta1, beta2, eps, (hipStream_t)stream));
-    h->step = t;
-    h->fwd_N = 0;                                           // the kept activations belong to the old parameters
-    return SDFA_OK;
+    return ts_adam(ts_of(h), MOD, lr, beta1, beta2, eps, stream);
 }
 
-int sdfa_lstmtrain_zero_grad(sdfa_lstmtrain *h, void *stream) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "lstmtrain_zero_grad: null handle");
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "lstmtrain_zero_grad: the handle is not finalised");
-    HIP_TRY(hipMemsetAsync(h->d_grad, 0, (size_t)h->off[NT] * sizeof(float), (hipStream_t)stream));
-    return SDFA_OK;
-}
+int sdfa_lstmtrain_zero_grad(sdfa_lstmtrain *h, void *stream) { return ts_zero_grad(ts_of(h), MOD, stream); }
 
 int sdfa_lstmtrain_get_tensor(sdfa_lstmtrain *h, const char *name, int what, float *h_dst, int64_t numel) {
-    if (!h_dst) return sdfa_fail(SDFA_EINVAL, "lstmtrain_get_tensor: null pointer");
-    const int ti = locate(h, "lstmtrain_get_tensor", name, numel);
-    if (ti < 0) return ti;
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "lstmtrain_get_tensor: the handle is not finalised");
-    const float *src = buffer_of(h, what);
-    if (!src) return sdfa_fail(SDFA_EINVAL, "lstmtrain_get_tensor: unknown buffer %d", what);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h_dst, src + h->off[ti], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-    return SDFA_OK;
+    const int ti = locate(h, "lstmtrain_get_tensor", name, h_dst, numel);
+    return ti < 0 ? ti : ts_get_tensor(h->ts, MOD, what, h->off[ti], h_dst, numel);
 }
 
 int sdfa_lstmtrain_set_state(sdfa_lstmtrain *h, const char *name, int what, const float *h_src, int64_t numel) {
-    if (!h_src) return sdfa_fail(SDFA_EINVAL, "lstmtrain_set_state: null pointer");
-    const int ti = locate(h, "lstmtrain_set_state", name, numel);
-    if (ti < 0) return ti;
-    if (!h->finalized) return sdfa_fail(SDFA_ESTATE, "lstmtrain_set_state: the handle is not finalised");
-    float *dst = buffer_of(h, what);
-    if (!dst) return sdfa_fail(SDFA_EINVAL, "lstmtrain_set_state: unknown buffer %d", what);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(dst + h->off[ti], h_src, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    if (what == SDFA_LSTMTRAIN_PARAM) h->fwd_N = 0;
-    return SDFA_OK;
+    const int ti = locate(h, "lstmtrain_set_state", name, h_src, numel);
+    return ti < 0 ? ti : ts_set_state(h->ts, MOD, what, h->off[ti], h_src, numel);
 }
 
 int sdfa_lstmtrain_set_grad(sdfa_lstmtrain *h, const char *name, const float *h_src, int64_t numel) {
     return sdfa_lstmtrain_set_state(h, name, SDFA_LSTMTRAIN_GRAD, h_src, numel);
 }
 
-int64_t sdfa_lstmtrain_step_count(const sdfa_lstmtrain *h) { return h ? h->step : sdfa_fail(SDFA_EINVAL, "lstmtrain_step_count: null handle"); }
-
-int sdfa_lstmtrain_set_step_count(sdfa_lstmtrain *h, int64_t t) {
-    if (!h) return sdfa_fail(SDFA_EINVAL, "lstmtrain_set_step_count: null handle");
-    if (t < 0) return sdfa_fail(SDFA_EINVAL, "lstmtrain_set_step_count: %lld is negative", (long long)t);
-    h->step = t;
-    return SDFA_OK;
-}
+int64_t sdfa_lstmtrain_step_count(const sdfa_lstmtrain *h) { return ts_step_count(ts_of(h), MOD); }
+int sdfa_lstmtrain_set_step_count(sdfa_lstmtrain *h, int64_t t) { return ts_set_step_count(ts_of(h), MOD, t); }
 
 }  // extern "C"

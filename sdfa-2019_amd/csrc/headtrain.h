@@ -1,6 +1,7 @@
 // Launchers of headtrain.hip for api_headtrain.cpp.
 #pragma once
 #include "../../include/sdfa_headtrain.h"
+#include "trainstate.h"      // HtAdamArgs, headtrain_adam, headtrain_adam_step: the three trainers share the Adam kernel
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -65,34 +66,7 @@ struct HtBwdArgs {
     int rowtiles, tkx;               // dX tiles along n and along k (Kin / 64)
 };
 
-struct HtAdamArgs {
-    float *p, *m, *v;
-    const float *g;
-    int64_t n;
-    float omb1, beta2, omb2, eps, step, bc2s;
-};
-
 hipError_t headtrain_fold(const HtTable &t, const float *params, float *W, float *inv, float *sc, hipStream_t st);
 hipError_t headtrain_forward_layer(const HtFwdArgs &a, hipStream_t st);
 hipError_t headtrain_backward_layer(const HtBwdArgs &a, hipStream_t st);
 hipError_t headtrain_wnorm_backward(const HtTable &t, const float *params, const float *dW, const float *inv, const float *sc, float *grads, hipStream_t st);
-hipError_t headtrain_adam(const HtAdamArgs &a, hipStream_t st);
-
-// Step t of torch.optim.Adam (amsgrad off, weight decay 0) over one flat buffer: the constants as the host forms them, both bias
-// corrections in double.  api_headtrain.cpp and api_attntrain.cpp launch the one kernel through this.
-inline hipError_t headtrain_adam_step(float *p, const float *g, float *m, float *v, int64_t n, int64_t t, double lr, double beta1,
-                                      double beta2, double eps, hipStream_t st) {
-    HtAdamArgs a;
-    a.p = p;
-    a.g = g;
-    a.m = m;
-    a.v = v;
-    a.n = n;
-    a.omb1 = (float)(1.0 - beta1);
-    a.beta2 = (float)beta2;
-    a.omb2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
-    a.step = (float)(lr / (1.0 - pow(beta1, (double)t)));
-    a.bc2s = (float)sqrt(1.0 - pow(beta2, (double)t));
-    return headtrain_adam(a, st);
-}

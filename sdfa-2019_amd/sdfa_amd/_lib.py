@@ -81,6 +81,17 @@ class SdfaError(RuntimeError):
         self.code = code
 
 
+def _bind_symbols(lib, symbols, stale):
+    """restype / argtypes of every symbol of a {name: (restype, argtypes)} table; a library without one of them is a stale build"""
+    for name, (res, args) in symbols.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(stale % f"symbol {name} is not exported") from None
+        fn.restype = res
+        fn.argtypes = args
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -96,17 +107,21 @@ def _load():
         raise ImportError(stale % "it does not export sdfa_abi_version") from None
     if have != ABI_VERSION:
         raise ImportError(stale % f"ABI version {have}, this binding needs {ABI_VERSION}")
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
+    _bind_symbols(lib, SYMBOLS, stale)
     return lib
 
 
 lib = _load()
+
+
+def bind(symbols, version_symbol, version, what):
+    """Bind the SYMBOLS table of a module whose header is versioned on its own: `version_symbol` (one of `symbols`) must answer the
+    `version` the module was written against; `what` is the header's word in the message ("headtrain")."""
+    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
+    _bind_symbols(lib, symbols, stale)
+    have = int(getattr(lib, version_symbol)())
+    if have != version:
+        raise ImportError(stale % f"{what} ABI version {have}, this binding needs {version}")
 
 
 option_epoch = 0      # bumped by every set_option: caches of results that a switch may change key on it (speech_anime signal -> z cache)

@@ -8,7 +8,7 @@ DESIGN.md section 19.
 A library without the symbols fails at import.  There is no CPU implementation."""
 import ctypes as C
 
-from ._lib import lib
+from ._lib import bind, lib
 
 ABI_VERSION = 1          # include/sdfa_bilstm.h SDFA_BILSTM_ABI_VERSION this binding was written against
 STEPS, FEATURES = 64, 256
@@ -20,18 +20,4 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_bilstm_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"bilstm ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_bilstm_abi_version", ABI_VERSION, "bilstm")

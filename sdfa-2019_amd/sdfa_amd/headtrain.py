@@ -7,18 +7,15 @@ saber_model.configure_optimizers builds it.  The contract is written down in the
 HeadTrainer owns the parameters, the gradients and the Adam state on the device; forward / backward / step are
 stream-ordered and read nothing back.  A library without the symbols fails at import.  There is no CPU implementation."""
 import ctypes as C
-import itertools
-import weakref
 
-import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import bind, lib, check
 from ._packed import ptr as _ptr, stream as _stream
+from ._trainer import PARAM, GRAD, EXP_AVG, EXP_AVG_SQ, Registry, Trainer
 
 ABI_VERSION = 1          # include/sdfa_headtrain.h SDFA_HEADTRAIN_ABI_VERSION this binding was written against
 HEAD_DGRAD, HEAD_OFFSETS = 0, 1
-PARAM, GRAD, EXP_AVG, EXP_AVG_SQ = 0, 1, 2, 3
 Z_DIM, SPEAKERS, TILE, MAX_ROWS = 512, 8, 64, 1 << 21
 LAUNCHES = {"dgrad": dict(forward=5, backward=5, adam=1), "offsets": dict(forward=4, backward=4, adam=1)}    # the fold is the forward's first
 
@@ -44,21 +41,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_headtrain_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"headtrain ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_headtrain_abi_version", ABI_VERSION, "headtrain")
 
 _BRANCH = ((512, 520), (256, 512), (None, 256))
 
@@ -84,17 +67,7 @@ def tensor_shapes(head):
     return t
 
 
-def _strip(name):
-    return name[len("_model."):] if name.startswith("_model.") else name
-
-
-def _f32(v):
-    if torch.is_tensor(v):
-        v = v.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(v, np.float32))
-
-
-class HeadTrainer:
+class HeadTrainer(Trainer):
     """The regressor head of a checkpoint with its gradients and Adam state on the device.
 
     state_dict: the reference's names, with or without "_model."; tensors of the encoder and the PCA are ignored.
@@ -102,34 +75,13 @@ class HeadTrainer:
     the trainer;  step() is one torch.optim.Adam step;  grads() / parameters() read back under the reference's names;
     state_dict() / load_state_dict() carry parameters, both moments and the step count, so a fit can resume."""
 
+    ABI = "headtrain"
+
     def __init__(self, state_dict, head, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, device=None):
         assert head in ("dgrad", "offsets"), head
         self.head = head
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.shapes = tensor_shapes(head)
-        self._h = None
-        h = lib.sdfa_headtrain_create(HEAD_DGRAD if head == "dgrad" else HEAD_OFFSETS)
-        if not h:
-            check(-1)
-        self._h = C.c_void_p(h)
-        self._finalizer = weakref.finalize(self, lib.sdfa_headtrain_destroy, self._h)
-        given = {_strip(k): v for k, v in state_dict.items()}
-        for name, shape in self.shapes.items():
-            if name not in given:
-                continue                                     # finalize names the first missing tensor
-            a = _f32(given[name])
-            check(lib.sdfa_headtrain_set_tensor(self._h, name.encode(), a.ctypes.data, a.size))
-        with torch.cuda.device(self.device):
-            check(lib.sdfa_headtrain_finalize(self._h, _stream()))
+        super().__init__(state_dict, tensor_shapes(head), (HEAD_DGRAD if head == "dgrad" else HEAD_OFFSETS,), lr, betas, eps, device)
         self.coef_dim = int(check(lib.sdfa_headtrain_coef_dim(self._h)))
-        self.numel = int(check(lib.sdfa_headtrain_numel(self._h)))
-        self._ws = None
-        self._n = 0
-
-    # ------------------------------------------------------------------------------------------------ the step
-    def workspace_bytes(self, rows):
-        return int(check(lib.sdfa_headtrain_workspace_bytes(self._h, int(rows))))
 
     def forward(self, z, speaker_id, check_ids=True):
         """z float32 cuda [N][512], speaker_id int64 [N] (host or device) -> coef float32 [N][Kc].  An id outside 0 .. 7 raises
@@ -143,12 +95,9 @@ class HeadTrainer:
         spk = torch.as_tensor(speaker_id).to(device=z.device, dtype=torch.int64).reshape(-1).contiguous()
         assert spk.numel() == N, (spk.shape, N)
         with torch.cuda.device(z.device):
-            need = self.workspace_bytes(N)
-            if self._ws is None or self._ws.numel() < need or self._ws.device != z.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=z.device)
+            ws = self._workspace(N, z.device)
             coef = torch.empty(N, self.coef_dim, dtype=torch.float32, device=z.device)
-            check(lib.sdfa_headtrain_forward(self._h, _ptr(z), _ptr(spk), N, _ptr(coef), _ptr(self._ws), self._ws.numel(), _stream()))
-        self._n = N
+            check(lib.sdfa_headtrain_forward(self._h, _ptr(z), _ptr(spk), N, _ptr(coef), _ptr(ws), ws.numel(), _stream()))
         return coef
 
     def backward(self, dcoef, want_dz=True):
@@ -163,79 +112,18 @@ class HeadTrainer:
             check(lib.sdfa_headtrain_backward(self._h, _ptr(dcoef), N, _ptr(dz) if want_dz else None, _ptr(ws), ws.numel(), _stream()))
         return dz
 
-    def step(self):
-        with torch.cuda.device(self.device):
-            check(lib.sdfa_headtrain_adam(self._h, self.lr, self.betas[0], self.betas[1], self.eps, _stream()))
-
-    def zero_grad(self):
-        with torch.cuda.device(self.device):
-            check(lib.sdfa_headtrain_zero_grad(self._h, _stream()))
-
-    # ------------------------------------------------------------------------------------------------ access
-    @property
-    def step_count(self):
-        return int(check(lib.sdfa_headtrain_step_count(self._h)))
-
-    def _read(self, what):
-        out = {}
-        with torch.cuda.device(self.device):
-            for name, shape in self.shapes.items():
-                a = np.empty(shape, np.float32)
-                check(lib.sdfa_headtrain_get_tensor(self._h, name.encode(), what, a.ctypes.data, a.size))
-                out[name] = a
-        return out
-
-    def _write(self, what, tensors):
-        with torch.cuda.device(self.device):
-            for name, v in tensors.items():
-                a = _f32(v)
-                check(lib.sdfa_headtrain_set_state(self._h, _strip(name).encode(), what, a.ctypes.data, a.size))
-
-    def parameters(self):
-        """{name without "_model.": float32 array} read back from the device."""
-        return self._read(PARAM)
-
-    def grads(self):
-        return self._read(GRAD)
-
-    def moments(self):
-        return self._read(EXP_AVG), self._read(EXP_AVG_SQ)
-
-    def set_grads(self, grads):
-        self._write(GRAD, grads)
-
     def head_state_dict(self, prefix="_model."):
         """The tuned head as torch tensors under the reference's names."""
-        return {prefix + k: torch.from_numpy(v) for k, v in self.parameters().items()}
+        return self.tuned_state_dict(prefix)
 
-    def state_dict(self):
-        m, v = self.moments()
-        return dict(head=self.head, params=self.parameters(), exp_avg=m, exp_avg_sq=v, step=self.step_count,
-                    lr=self.lr, betas=self.betas, eps=self.eps)
+    def _state_extra(self):
+        return dict(head=self.head)
 
     def load_state_dict(self, state):
         assert state["head"] == self.head, (state["head"], self.head)
-        self._write(PARAM, state["params"])
-        self._write(EXP_AVG, state["exp_avg"])
-        self._write(EXP_AVG_SQ, state["exp_avg_sq"])
-        check(lib.sdfa_headtrain_set_step_count(self._h, int(state["step"])))
-        self.lr, self.betas, self.eps = float(state["lr"]), tuple(float(b) for b in state["betas"]), float(state["eps"])
-        return self
+        return super().load_state_dict(state)
 
 
-# trainers the custom op torch.ops.sdfa.head_train finds by key; weak, as the model registry of sdfa_amd.ops is
-_TRAINERS = weakref.WeakValueDictionary()
-_ANON = itertools.count(1)
-
-
-def register_trainer(trainer, key=None):
-    key = f"sdfa-head-trainer-{next(_ANON)}" if key is None else str(key)
-    _TRAINERS[key] = trainer
-    return key
-
-
-def trainer_of(key):
-    try:
-        return _TRAINERS[key]
-    except KeyError:
-        raise KeyError(f"sdfa: no head trainer registered as {key!r} (sdfa_amd.headtrain.register_trainer)") from None
+# trainers the custom op torch.ops.sdfa.head_train finds by key
+_REGISTRY = Registry("head", "head")
+register_trainer, trainer_of = _REGISTRY.register, _REGISTRY.find

@@ -7,7 +7,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import lib, check, SdfaError
+from ._lib import bind, lib, check, SdfaError
 from ._packed import PackedReadback, ptr as _ptr, stream as _stream
 from .render import CHUNK_FRAMES
 
@@ -27,21 +27,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_jpeg_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"jpeg ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_jpeg_abi_version", ABI_VERSION, "jpeg")
 
 
 class PendingChunk(PackedReadback):

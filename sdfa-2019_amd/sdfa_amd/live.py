@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import bind, lib, check
 from .engine import FEAT_SHAPE, FPS, TS_DELTA_MS, frame_geometry
 
 ABI_VERSION = 1      # include/sdfa_stream.h SDFA_STREAM_ABI_VERSION this binding was written against
@@ -44,21 +44,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_stream_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"stream ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_stream_abi_version", ABI_VERSION, "stream")
 
 
 def frame_positions(k0, count, sr, fps=FPS, ts_delta=TS_DELTA_MS):

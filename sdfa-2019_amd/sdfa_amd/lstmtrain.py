@@ -7,17 +7,14 @@ sdfa_amd.attntrain produces.  The contract is written down in the header and in 
 LstmTrainer owns the parameters, the gradients and the Adam state on the device; forward / backward / step are stream-ordered
 and read nothing back.  A library without the symbols fails at import.  There is no CPU implementation."""
 import ctypes as C
-import itertools
-import weakref
 
-import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import bind, lib, check
 from ._packed import ptr as _ptr, stream as _stream
+from ._trainer import PARAM, GRAD, EXP_AVG, EXP_AVG_SQ, Registry, Trainer
 
 ABI_VERSION = 1          # include/sdfa_lstmtrain.h SDFA_LSTMTRAIN_ABI_VERSION this binding was written against
-PARAM, GRAD, EXP_AVG, EXP_AVG_SQ = 0, 1, 2, 3
 STEPS, HIDDEN, GATES, OUT, TILE_FRAMES, BLOCK_FRAMES, MAX_FRAMES = 64, 256, 1024, 512, 32, 32, 3072
 IN_DIM = {0: 256, 1: 512}
 LAUNCHES = dict(forward=3, backward=3, adam=1)
@@ -45,21 +42,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_lstmtrain_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"lstmtrain ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_lstmtrain_abi_version", ABI_VERSION, "lstmtrain")
 
 
 def tensor_shapes(layer):
@@ -72,17 +55,7 @@ def tensor_shapes(layer):
     return out
 
 
-def _strip(name):
-    return name[len("_model."):] if name.startswith("_model.") else name
-
-
-def _f32(v):
-    if torch.is_tensor(v):
-        v = v.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(v, np.float32))
-
-
-class LstmTrainer:
+class LstmTrainer(Trainer):
     """One layer of a checkpoint's BiLSTM with its gradients and Adam state on the device.
 
     state_dict: the reference's names, with or without "_model."; every other tensor is ignored.
@@ -91,34 +64,15 @@ class LstmTrainer:
     torch.optim.Adam step;  grads() / parameters() read back under the reference's names;  state_dict() / load_state_dict() carry
     parameters, both moments and the step count, so a fit can resume."""
 
+    ABI = "lstmtrain"
+
     def __init__(self, state_dict, layer=1, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, device=None, want_dX=True):
         self.layer = int(layer)
         self.want_dX = bool(want_dX)          # what the backward of torch.ops.sdfa.lstm_train returns for X
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.shapes = tensor_shapes(self.layer)
+        shapes = tensor_shapes(self.layer)
         self.in_dim = IN_DIM[self.layer]
-        self._h = None
-        h = lib.sdfa_lstmtrain_create(self.in_dim)
-        if not h:
-            check(-1)
-        self._h = C.c_void_p(h)
-        self._finalizer = weakref.finalize(self, lib.sdfa_lstmtrain_destroy, self._h)
-        given = {_strip(k): v for k, v in state_dict.items()}
-        for name in self.shapes:
-            if name not in given:
-                continue                                     # finalize names the first missing tensor
-            a = _f32(given[name])
-            check(lib.sdfa_lstmtrain_set_tensor(self._h, name.encode(), a.ctypes.data, a.size))
-        with torch.cuda.device(self.device):
-            check(lib.sdfa_lstmtrain_finalize(self._h, _stream()))
-        self.numel = int(check(lib.sdfa_lstmtrain_numel(self._h)))
-        self._ws = None
+        super().__init__(state_dict, shapes, (self.in_dim,), lr, betas, eps, device)
         self._X = self._Y = None
-
-    # ------------------------------------------------------------------------------------------------ the step
-    def workspace_bytes(self, frames):
-        return int(check(lib.sdfa_lstmtrain_workspace_bytes(self._h, int(frames))))
 
     def forward(self, X):
         """X float32 cuda [N][64][I] -> Y float32 [N][64][512].  X and Y are kept (not copied) for the backward."""
@@ -127,11 +81,9 @@ class LstmTrainer:
         X = X.detach().contiguous()
         N = int(X.shape[0])
         with torch.cuda.device(X.device):
-            need = self.workspace_bytes(N)
-            if self._ws is None or self._ws.numel() < need or self._ws.device != X.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=X.device)
+            ws = self._workspace(N, X.device)
             Y = torch.empty(N, STEPS, OUT, dtype=torch.float32, device=X.device)
-            check(lib.sdfa_lstmtrain_forward(self._h, _ptr(X), N, _ptr(Y), _ptr(self._ws), self._ws.numel(), _stream()))
+            check(lib.sdfa_lstmtrain_forward(self._h, _ptr(X), N, _ptr(Y), _ptr(ws), ws.numel(), _stream()))
         self._X, self._Y = X, Y
         return Y
 
@@ -150,81 +102,21 @@ class LstmTrainer:
             check(lib.sdfa_lstmtrain_backward(self._h, _ptr(X), _ptr(Y), _ptr(dY), N, _ptr(dX) if want_dX else None, _ptr(ws), ws.numel(), _stream()))
         return dX
 
-    def step(self):
-        with torch.cuda.device(self.device):
-            check(lib.sdfa_lstmtrain_adam(self._h, self.lr, self.betas[0], self.betas[1], self.eps, _stream()))
+    def _forget(self):
         self._X = self._Y = None
-
-    def zero_grad(self):
-        with torch.cuda.device(self.device):
-            check(lib.sdfa_lstmtrain_zero_grad(self._h, _stream()))
-
-    # ------------------------------------------------------------------------------------------------ access
-    @property
-    def step_count(self):
-        return int(check(lib.sdfa_lstmtrain_step_count(self._h)))
-
-    def _read(self, what):
-        out = {}
-        with torch.cuda.device(self.device):
-            for name, shape in self.shapes.items():
-                a = np.empty(shape, np.float32)
-                check(lib.sdfa_lstmtrain_get_tensor(self._h, name.encode(), what, a.ctypes.data, a.size))
-                out[name] = a
-        return out
-
-    def _write(self, what, tensors):
-        with torch.cuda.device(self.device):
-            for name, v in tensors.items():
-                a = _f32(v)
-                check(lib.sdfa_lstmtrain_set_state(self._h, _strip(name).encode(), what, a.ctypes.data, a.size))
-
-    def parameters(self):
-        """{name without "_model.": float32 array} read back from the device."""
-        return self._read(PARAM)
-
-    def grads(self):
-        return self._read(GRAD)
-
-    def moments(self):
-        return self._read(EXP_AVG), self._read(EXP_AVG_SQ)
-
-    def set_grads(self, grads):
-        self._write(GRAD, grads)
 
     def lstm_state_dict(self, prefix="_model."):
         """The tuned layer as torch tensors under the reference's names."""
-        return {prefix + k: torch.from_numpy(v) for k, v in self.parameters().items()}
+        return self.tuned_state_dict(prefix)
 
-    def state_dict(self):
-        m, v = self.moments()
-        return dict(params=self.parameters(), exp_avg=m, exp_avg_sq=v, step=self.step_count, lr=self.lr, betas=self.betas, eps=self.eps,
-                    layer=self.layer)
+    def _state_extra(self):
+        return dict(layer=self.layer)
 
     def load_state_dict(self, state):
         assert int(state.get("layer", self.layer)) == self.layer, (state.get("layer"), self.layer)
-        self._write(PARAM, state["params"])
-        self._write(EXP_AVG, state["exp_avg"])
-        self._write(EXP_AVG_SQ, state["exp_avg_sq"])
-        check(lib.sdfa_lstmtrain_set_step_count(self._h, int(state["step"])))
-        self.lr, self.betas, self.eps = float(state["lr"]), tuple(float(b) for b in state["betas"]), float(state["eps"])
-        self._X = self._Y = None
-        return self
+        return super().load_state_dict(state)
 
 
-# trainers the custom op torch.ops.sdfa.lstm_train finds by key; weak, as the model registry of sdfa_amd.ops is
-_TRAINERS = weakref.WeakValueDictionary()
-_ANON = itertools.count(1)
-
-
-def register_trainer(trainer, key=None):
-    key = f"sdfa-lstm-trainer-{next(_ANON)}" if key is None else str(key)
-    _TRAINERS[key] = trainer
-    return key
-
-
-def trainer_of(key):
-    try:
-        return _TRAINERS[key]
-    except KeyError:
-        raise KeyError(f"sdfa: no BiLSTM trainer registered as {key!r} (sdfa_amd.lstmtrain.register_trainer)") from None
+# trainers the custom op torch.ops.sdfa.lstm_train finds by key
+_REGISTRY = Registry("lstm", "BiLSTM")
+register_trainer, trainer_of = _REGISTRY.register, _REGISTRY.find

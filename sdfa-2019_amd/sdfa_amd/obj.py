@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import bind, lib, check
 from ._packed import PackedReadback, ptr as _ptr, stream as _stream
 from .jpeg import CHUNK_BYTES
 from .render import CHUNK_FRAMES
@@ -29,21 +29,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_obj_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"obj ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_obj_abi_version", ABI_VERSION, "obj")
 
 
 def format_faces(faces, n_verts):

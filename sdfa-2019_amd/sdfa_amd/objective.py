@@ -14,7 +14,7 @@ import weakref
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import bind, lib, check
 from ._packed import ptr as _ptr, stream as _stream
 
 ABI_VERSION = 1          # include/sdfa_objective.h SDFA_OBJECTIVE_ABI_VERSION this binding was written against
@@ -30,21 +30,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_objective_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"objective ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_objective_abi_version", ABI_VERSION, "objective")
 
 
 class Bases:

@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._lib import lib, check, SdfaError
+from ._lib import bind, lib, check, SdfaError
 from ._packed import ptr as _ptr, stream as _stream
 
 ABI_VERSION = 1          # include/sdfa_pca.h SDFA_PCA_ABI_VERSION this binding was written against
@@ -41,21 +41,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_pca_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"pca ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_pca_abi_version", ABI_VERSION, "pca")
 
 
 class PcaNotConverged(SdfaError):

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import lib, check, SdfaError
+from ._lib import bind, lib, check, SdfaError
 
 ABI_VERSION = 1      # include/sdfa_render.h SDFA_RENDER_ABI_VERSION this binding was written against
 NORMALS = {"template": 0, "frame": 1}
@@ -34,21 +34,7 @@ SYMBOLS = {
 }
 
 
-def _bind():
-    stale = "libsdfa_hip.so is a stale build (%s): rebuild it with `make -C sdfa-2019_amd/csrc`.  There is no CPU fallback."
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % f"symbol {name} is not exported") from None
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.sdfa_render_abi_version())
-    if have != ABI_VERSION:
-        raise ImportError(stale % f"render ABI version {have}, this binding needs {ABI_VERSION}")
-
-
-_bind()
+bind(SYMBOLS, "sdfa_render_abi_version", ABI_VERSION, "render")
 
 
 def default_params():
