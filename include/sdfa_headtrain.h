@@ -23,7 +23,8 @@
  *              then + W[p][512 + speaker] where the layer takes the one-hot; lrelu is max(x, 0.2f x), tanh is tanhf.
  *           The one-hot columns are never materialised.  Kept in the workspace: z, the speaker ids, the layer outputs.
  * Backward  per depth one launch; block index tells a layer's dW + db tiles from its dX tiles.
- *               dW[p][k] = sum_n dPre[n][p] x[n][k] (n ascending in one fp32 MFMA chain; the contraction is not split);
+ *               dW[p][k] = sum_n dPre[n][p] x[n][k] (n ascending in one fp32 MFMA chain per row block of 4,096 rows; a batch of
+ *               more than 4,096 rows leaves float32 partials, and one more launch adds them in ascending block order);
  *               dW[p][512 + s] = sum over the rows of speaker s of dPre[n][p];  db[p] = sum_n dPre[n][p]
  *               dX[n][k] = sum_p dPre[n][p] W[p][k], k < 512 (the one-hot part is discarded)
  *               dPre of the layer below = dX * (y > 0 ? 1 : 0.2f) for lrelu, dX * fma(-y, y, 1) for tanh, y the kept output;
@@ -37,7 +38,8 @@
  *           An element whose gradient has been exactly 0 at every step keeps its bits.
  * Sums      no atomics, no workgroup waits on another.  Every sum's order depends on the shape alone: the same inputs give
  *           the same bits, and a row's coef and dz do not depend on the other rows of the batch.
- * Launches  DGRAD: 1 + 4 (forward) + 4 + 1 (backward) + 1 (Adam) = 11;  OFFSETS: 1 + 3 + 3 + 1 + 1 = 9.
+ * Launches  DGRAD: 1 + 4 (forward) + 4 + 1 (backward) + 1 (Adam) = 11;  OFFSETS: 1 + 3 + 3 + 1 + 1 = 9;  one more in the backward of
+ *           a batch of more than 4,096 rows (the row blocks' reduce).
  */
 #ifndef SDFA_HEADTRAIN_H
 #define SDFA_HEADTRAIN_H

@@ -32,7 +32,8 @@ const Spec OFFSETS[3] = {
 
 // Workspace of a batch of N rows, offsets in floats, every buffer on a 256-byte boundary.
 struct Ws {
-    int64_t z, sid, h0, h1[2], h2[2], d2[2], d1[2], d0, total;
+    int64_t z, sid, h0, h1[2], h2[2], d2[2], d1[2], d0, partW, partb, total;
+    int nblk;                            // row blocks of the dW | db contraction; their partials exist for more than one
 };
 
 const char *const MOD = "headtrain";
@@ -69,6 +70,9 @@ Ws ws_layout(const sdfa_headtrain *h, int64_t N) {
         w.d2[b] = on ? take(N * 256) : 0;
         w.d1[b] = on ? take(N * 512) : 0;
     }
+    w.nblk = (int)((N + HT_BLOCK_ROWS - 1) / HT_BLOCK_ROWS);
+    w.partW = w.nblk > 1 ? take(w.nblk * h->wnumel) : 0;
+    w.partb = w.nblk > 1 ? take((int64_t)w.nblk * h->t.rows) : 0;
     w.total = take.bytes();
     return w;
 }
@@ -127,7 +131,7 @@ HtFwdJob fwd_job(const sdfa_headtrain *h, int li, const float *X, int ldx, float
     return j;
 }
 
-HtBwdJob bwd_job(const sdfa_headtrain *h, int li, const float *D, int ldd, const float *X, const float *Yprev, float *Dprev) {
+HtBwdJob bwd_job(const sdfa_headtrain *h, const Ws &w, float *f, int li, const float *D, int ldd, const float *X, const float *Yprev, float *Dprev) {
     const HtLayer &L = h->t.l[li];
     HtBwdJob j;
     j.D = D;
@@ -135,6 +139,8 @@ HtBwdJob bwd_job(const sdfa_headtrain *h, int li, const float *D, int ldd, const
     j.W = h->d_W + L.ow;
     j.dW = h->d_dW + L.ow;
     j.db = h->ts.d_grad + L.ob;
+    j.pW = f + w.partW + L.ow;
+    j.pb = f + w.partb + L.row0;
     j.Yprev = Yprev;
     j.Dprev = Dprev;
     j.ldd = ldd;
@@ -294,13 +300,16 @@ int sdfa_headtrain_backward(sdfa_headtrain *h, const float *d_dcoef, int64_t N, 
     a.sid = (const int *)(f + w.sid);
     a.nb = h->nb;
     a.rowtiles = (int)((N + SDFA_HEADTRAIN_TILE - 1) / SDFA_HEADTRAIN_TILE);
+    a.nblk = w.nblk;
+    a.psw = h->wnumel;
+    a.psb = h->t.rows;
     for (int depth = 2; depth >= 0; --depth) {
         int coff = 0;
         for (int b = 0; b < h->nb; ++b) {
             const int li = l1 + 3 * b + depth;
-            if (depth == 2) a.b[b] = bwd_job(h, li, d_dcoef + coff, h->kc, f + w.h2[b], f + w.h2[b], f + w.d2[b]);
-            else if (depth == 1) a.b[b] = bwd_job(h, li, f + w.d2[b], 256, f + w.h1[b], f + w.h1[b], f + w.d1[b]);
-            else a.b[b] = bwd_job(h, li, f + w.d1[b], 512, x1, dg ? f + w.h0 : nullptr, dg ? f + w.d0 : d_dz);
+            if (depth == 2) a.b[b] = bwd_job(h, w, f, li, d_dcoef + coff, h->kc, f + w.h2[b], f + w.h2[b], f + w.d2[b]);
+            else if (depth == 1) a.b[b] = bwd_job(h, w, f, li, f + w.d2[b], 256, f + w.h1[b], f + w.h1[b], f + w.d1[b]);
+            else a.b[b] = bwd_job(h, w, f, li, f + w.d1[b], 512, x1, dg ? f + w.h0 : nullptr, dg ? f + w.d0 : d_dz);
             coff += h->t.l[li].P;
         }
         if (h->nb == 1) a.b[1] = a.b[0];
@@ -322,11 +331,22 @@ int sdfa_headtrain_backward(sdfa_headtrain *h, const float *d_dcoef, int64_t N, 
     }
     if (dg) {
         a.nb = 1;
-        a.b[0] = a.b[1] = bwd_job(h, 0, f + w.d0, 512, f + w.z, nullptr, d_dz);
+        a.b[0] = a.b[1] = bwd_job(h, w, f, 0, f + w.d0, 512, f + w.z, nullptr, d_dz);
         a.tkx = a.b[0].Kin / SDFA_HEADTRAIN_TILE;
         a.dx_mode = d_dz ? HT_DX_PLAIN : HT_DX_NONE;
         a.act_prev = HT_ACT_LINEAR;
         HIP_TRY(headtrain_backward_layer(a, st));
+    }
+    if (w.nblk > 1) {
+        HtReduceArgs r;
+        r.t = h->t;
+        r.pW = f + w.partW;
+        r.pb = f + w.partb;
+        r.dW = h->d_dW;
+        r.grads = h->ts.d_grad;
+        r.wnumel = h->wnumel;
+        r.nblk = w.nblk;
+        HIP_TRY(headtrain_reduce(r, st));
     }
     HIP_TRY(headtrain_wnorm_backward(h->t, h->ts.d_param, h->d_dW, h->d_inv, h->d_sc, h->ts.d_grad, st));
     return SDFA_OK;

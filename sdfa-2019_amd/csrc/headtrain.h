@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 constexpr int HT_MAX_LAYERS = 7;
+constexpr int HT_BLOCK_ROWS = 4096;  // rows of one row block of the dW | db contraction: 64 row tiles
 enum { HT_ACT_LINEAR = 0, HT_ACT_LRELU = 1, HT_ACT_TANH = 2 };
 
 // One fully connected layer inside the flat buffers.  Parameters, gradients and both moments share one layout (per layer
@@ -48,6 +49,7 @@ struct HtBwdJob {
     const float *X;                  // the layer's input [N][Kin], row stride ldx
     const float *W;                  // [P][K]
     float *dW, *db;                  // [P][K], [P]
+    float *pW, *pb;                  // the row blocks' partials of dW and db, block strides psw and psb (more than one row block only)
     const float *Yprev;              // output of the layer below (what X is), for its activation's derivative
     float *Dprev;                    // dPre of the layer below [N][Kin], or dz
     int ldd, ldx, ldp, P, K, Kin, cond;
@@ -64,9 +66,20 @@ struct HtBwdArgs {
     int dx_mode;                     // NONE: no dX tiles; BRANCH: each branch's own, times act'; MERGE: both branches into one, times act'; PLAIN: dz
     int act_prev;
     int rowtiles, tkx;               // dX tiles along n and along k (Kin / 64)
+    int nblk;                        // row blocks of HT_BLOCK_ROWS rows; 1: the dW tiles write dW and db themselves
+    int64_t psw, psb;                // floats between two row blocks' partials of dW (all layers' W) and of db (all layers' rows)
+};
+
+struct HtReduceArgs {
+    HtTable t;
+    const float *pW, *pb;            // [nblk][wnumel], [nblk][rows]
+    float *dW, *grads;               // dW [wnumel]; db goes to its place in the gradient buffer
+    int64_t wnumel;
+    int nblk;
 };
 
 hipError_t headtrain_fold(const HtTable &t, const float *params, float *W, float *inv, float *sc, hipStream_t st);
 hipError_t headtrain_forward_layer(const HtFwdArgs &a, hipStream_t st);
 hipError_t headtrain_backward_layer(const HtBwdArgs &a, hipStream_t st);
+hipError_t headtrain_reduce(const HtReduceArgs &a, hipStream_t st);
 hipError_t headtrain_wnorm_backward(const HtTable &t, const float *params, const float *dW, const float *inv, const float *sc, float *grads, hipStream_t st);

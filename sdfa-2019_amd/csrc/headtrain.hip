@@ -145,8 +145,9 @@ __device__ __forceinline__ void dx_acc(f32x16 &acc, const HtBwdJob &jb, int64_t 
     tile_acc<true, false>(acc, jb.P, opA, opB, sA, sB);
 }
 
-// grid: x = [branch 0's dW tiles | branch 1's dW tiles | dX tiles].  The dW tiles contract over all N rows and run longest:
-// they come first.
+// grid: x = [per row block: branch 0's dW tiles | branch 1's dW tiles] [dX tiles].  The dW tiles contract over a row block of up
+// to HT_BLOCK_ROWS rows and run longest: they come first.  A batch of more than one row block leaves float32 partials, which the
+// reduce launch adds in ascending block order: no accumulator chain is longer than a row block, whatever N.
 __global__ __launch_bounds__(THREADS) void headtrain_backward_kernel(HtBwdArgs a) {
     __shared__ float sA[CH * LP], sB[CH * LP];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
@@ -155,50 +156,56 @@ __global__ __launch_bounds__(THREADS) void headtrain_backward_kernel(HtBwdArgs a
     const int ndw = a.b[0].ndw + (a.nb == 2 ? a.b[1].ndw : 0);
     f32x16 acc;
     zero(acc);
-    if (bid < ndw) {
-        // dW[p][k] = sum_n D[n][p] x[n][k]; x's columns Kin .. K - 1 are the one-hot, column K is 1: that one is db
+    if (bid < ndw * a.nblk) {
+        // a row block's share of dW[p][k] = sum_n D[n][p] x[n][k]; x's columns Kin .. K - 1 are the one-hot, column K is 1: that
+        // one is db.  Rows r0 .. r0 + C - 1; a batch of one row block is the whole contraction and goes to dW and db itself.
+        const int blk = bid / ndw;
+        bid -= blk * ndw;
         const int br = bid < a.b[0].ndw ? 0 : 1;
         const HtBwdJob jb = a.b[br];
         if (br) bid -= a.b[0].ndw;
         const int p0 = (bid / jb.tk) * T, k0 = (bid % jb.tk) * T;
+        const int64_t r0 = (int64_t)blk * HT_BLOCK_ROWS;
+        const int C = (int)(N - r0 < HT_BLOCK_ROWS ? N - r0 : HT_BLOCK_ROWS);
         struct {
             const HtBwdJob &jb;
-            int p0;
-            int64_t N;
+            int p0, C;
+            int64_t r0;
             __device__ const float *at(int i, int c) const {
-                return jb.D + (int64_t)(c < N ? c : N - 1) * jb.ldd + (p0 + i < jb.P ? p0 + i : jb.P - 1);
+                return jb.D + (r0 + (c < C ? c : C - 1)) * jb.ldd + (p0 + i < jb.P ? p0 + i : jb.P - 1);
             }
-            __device__ float val(int i, int c, float v) const { return p0 + i < jb.P && c < N ? v : 0.f; }
-        } opA{jb, p0, N};
+            __device__ float val(int i, int c, float v) const { return p0 + i < jb.P && c < C ? v : 0.f; }
+        } opA{jb, p0, C, r0};
         struct {
             const HtBwdJob &jb;
-            int k0;
-            int64_t N;
+            int k0, C;
+            int64_t r0;
             const int *sid;
             __device__ const float *at(int j, int c) const {
-                return jb.X + (int64_t)(c < N ? c : N - 1) * jb.ldx + (k0 + j < jb.Kin ? k0 + j : jb.Kin - 1);
+                return jb.X + (r0 + (c < C ? c : C - 1)) * jb.ldx + (k0 + j < jb.Kin ? k0 + j : jb.Kin - 1);
             }
             __device__ float val(int j, int c, float v) const {
                 const int k = k0 + j;
-                if (c >= N || k > jb.K) return 0.f;
+                if (c >= C || k > jb.K) return 0.f;
                 if (k < jb.Kin) return v;
                 if (k == jb.K) return 1.f;
-                return sid[c] == k - jb.Kin ? 1.f : 0.f;     // the last tile along k only
+                return sid[r0 + c] == k - jb.Kin ? 1.f : 0.f;     // the last tile along k only
             }
-        } opB{jb, k0, N, a.sid};
-        tile_acc<false, false>(acc, (int)N, opA, opB, sA, sB);
+        } opB{jb, k0, C, r0, a.sid};
+        tile_acc<false, false>(acc, C, opA, opB, sA, sB);
+        float *dW = a.nblk == 1 ? jb.dW : jb.pW + blk * a.psw, *db = a.nblk == 1 ? jb.db : jb.pb + blk * a.psb;
         const int k = k0 + 32 * (wave & 1) + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int p = p0 + 32 * (wave >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
             if (p >= jb.P) continue;
-            if (k < jb.K) jb.dW[(int64_t)p * jb.K + k] = acc[r];
-            else if (k == jb.K) jb.db[p] = acc[r];
+            if (k < jb.K) dW[(int64_t)p * jb.K + k] = acc[r];
+            else if (k == jb.K) db[p] = acc[r];
         }
         return;
     }
     // dX[n][k] = sum_p D[n][p] W[p][k], k < Kin
-    bid -= ndw;
+    bid -= ndw * a.nblk;
     const int tiles = a.rowtiles * a.tkx;
     const int br = a.dx_mode == HT_DX_BRANCH ? bid / tiles : 0;
     bid -= br * tiles;
@@ -226,6 +233,24 @@ __global__ __launch_bounds__(THREADS) void headtrain_backward_kernel(HtBwdArgs a
         }
         jb.Dprev[n * jb.ldp + k] = v;
     }
+}
+
+// dW and db of a batch of more than one row block: the row blocks' partials, ascending.  An element per thread.
+__global__ __launch_bounds__(256) void headtrain_reduce_kernel(HtReduceArgs a) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.wnumel + a.t.rows) return;
+    const bool w = e < a.wnumel;
+    const float *src = w ? a.pW + e : a.pb + (e - a.wnumel);
+    const int64_t stride = w ? a.wnumel : a.t.rows;
+    float s = 0.f;
+    for (int b = 0; b < a.nblk; ++b) s = fadd_exact(s, src[b * stride]);
+    if (w) {
+        a.dW[e] = s;
+        return;
+    }
+    const int row = (int)(e - a.wnumel);
+    const HtLayer L = a.t.l[layer_of(a.t, row)];
+    a.grads[L.ob + row - L.row0] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------- Adam
@@ -263,9 +288,14 @@ hipError_t headtrain_forward_layer(const HtFwdArgs &a, hipStream_t st) {
 }
 
 hipError_t headtrain_backward_layer(const HtBwdArgs &a, hipStream_t st) {
-    int64_t blocks = a.b[0].ndw + (a.nb == 2 ? a.b[1].ndw : 0);
+    int64_t blocks = (int64_t)a.nblk * (a.b[0].ndw + (a.nb == 2 ? a.b[1].ndw : 0));
     if (a.dx_mode != HT_DX_NONE) blocks += (int64_t)a.rowtiles * a.tkx * (a.dx_mode == HT_DX_BRANCH ? a.nb : 1);
     hipLaunchKernelGGL(headtrain_backward_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t headtrain_reduce(const HtReduceArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(headtrain_reduce_kernel, dim3((unsigned)((a.wnumel + a.t.rows + 255) / 256)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -17,7 +17,7 @@ from ._trainer import PARAM, GRAD, EXP_AVG, EXP_AVG_SQ, Registry, Trainer
 ABI_VERSION = 1          # include/sdfa_headtrain.h SDFA_HEADTRAIN_ABI_VERSION this binding was written against
 HEAD_DGRAD, HEAD_OFFSETS = 0, 1
 Z_DIM, SPEAKERS, TILE, MAX_ROWS = 512, 8, 64, 1 << 21
-LAUNCHES = {"dgrad": dict(forward=5, backward=5, adam=1), "offsets": dict(forward=4, backward=4, adam=1)}    # the fold is the forward's first
+LAUNCHES = {"dgrad": dict(forward=5, backward=5, adam=1), "offsets": dict(forward=4, backward=4, adam=1)}    # the fold is the forward's first; above 4,096 rows the backward has one more, the row blocks' reduce
 
 _p, _i64, _f64 = C.c_void_p, C.c_int64, C.c_double
 SYMBOLS = {

@@ -71,10 +71,11 @@ def _q(*terms):
     return np.sqrt(sum(t * t for t in terms))
 
 
-def run(params, H, dz=None, dparams=None, flaw=None, ddz=None):
+def run(params, H, dz=None, dparams=None, flaw=None, ddz=None, pieces=False):
     """float32 inputs -> dict: z, align, dH, grads {name: array} in float64 and their kappas k_z, k_align, k_dH, k_grads.
     dz None: forward only.  ddz: kappa of dz where it is not an exact input (the head's backward produced it); its elements
-    are features of a contraction: quadrature."""
+    are features of a contraction: quadrature.  pieces: also `pieces`, the operands of the gradients' contractions over rows and
+    frames with their sigmas, frame by frame (tests/bigbatch_ref64.py sums them with other frame weights)."""
     assert flaw is None or flaw in FLAWS, flaw
     H = _f64(H)
     N = len(H)
@@ -167,6 +168,9 @@ def run(params, H, dz=None, dparams=None, flaw=None, ddz=None):
         dH[:, w0:w0 + KW] += dHq
         e_dH[:, w0:w0 + KW] += e_dHq + U * np.abs(dH[:, w0:w0 + KW])
     out.update(dH=dH, k_dH=LAMBDA * e_dH, grads=grads, k_grads=kg)
+    if pieces:
+        out["pieces"] = dict(H=H, hq=hq, qc=qc, e_qc=e_qc, u=u, e_u=e_u, ds=ds, e_ds=e_ds, dpre=dpre, e_dpre=e_dpre, dqp=dqp, e_dqp=e_dqp,
+                             dqc=dqc, e_dqc=e_dqc)
     return out
 
 

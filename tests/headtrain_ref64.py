@@ -125,9 +125,28 @@ def _onehot(sid, flaw):
     return np.eye(8)[s]
 
 
-def run(head, params, z, sid, dcoef=None, dparams=None, flaw=None, slope=SLOPE32):
+def weight_norm_backward(f, K, dW, edW, flaw=None):
+    """dW of the folded weight and its sigma through the weight norm of the fold `f` (a _Layer):
+    -> (dg, kappa of dg, dv, kappa of dv), dg as a column."""
+    dot = (dW * f.v).sum(1)
+    edot = np.sqrt(((edW * f.v) ** 2 + (dW * f.ev) ** 2).sum(1)) + np.sqrt(K + 1) * U * np.abs(dW * f.v).sum(1)
+    dg = dot * f.inv
+    edg = edot * f.inv + np.abs(dot) * f.einv + U * np.abs(dg)
+    c = dg * f.inv
+    ec = edg * f.inv + np.abs(dg) * f.einv + U * np.abs(c)
+    if flaw == "no_proj":
+        c = np.zeros_like(c)
+    t = dW - c[:, None] * f.v
+    et = edW + ec[:, None] * np.abs(f.v) + np.abs(c)[:, None] * f.ev + U * np.abs(c[:, None] * f.v) + U * np.abs(t)
+    dv = f.s[:, None] * t
+    return dg.reshape(-1, 1), LAMBDA * edg.reshape(-1, 1), dv, LAMBDA * (f.es[:, None] * np.abs(t) + np.abs(f.s)[:, None] * et + U * np.abs(dv))
+
+
+def run(head, params, z, sid, dcoef=None, dparams=None, flaw=None, slope=SLOPE32, pieces=False):
     """float32 inputs -> dict: coef, dz, grads {name: array} in float64, their kappas k_coef, k_dz, k_grads, and `ambiguous`,
-    the number of lrelu outputs whose sign the bound cannot tell.  dcoef None: forward only."""
+    the number of lrelu outputs whose sign the bound cannot tell.  dcoef None: forward only.  pieces: also `pieces`, per layer
+    the operands of its contraction over the rows (dPre, its sigma, the layer's input with the one-hot columns, its sigma), and
+    `fold`, the layers' folds (tests/bigbatch_ref64.py sums them with other row weights)."""
     assert flaw is None or flaw in FLAWS, flaw
     z, N = _f64(z), len(z)
     oh = _onehot(sid, flaw)
@@ -195,23 +214,10 @@ def run(head, params, z, sid, dcoef=None, dparams=None, flaw=None, slope=SLOPE32
         dX = D @ f.W[:, :Kin]
         edX = np.sqrt((eD * eD) @ (f.W[:, :Kin] ** 2) + (D * D) @ (f.eW[:, :Kin] ** 2)
                       + (np.sqrt(L["P"] + 1) * U * (aD @ np.abs(f.W[:, :Kin]))) ** 2)
-        # through the weight norm
-        dot = (dW * f.v).sum(1)
-        edot = np.sqrt(((edW * f.v) ** 2 + (dW * f.ev) ** 2).sum(1)) + np.sqrt(K + 1) * U * np.abs(dW * f.v).sum(1)
-        dg = dot * f.inv
-        edg = edot * f.inv + np.abs(dot) * f.einv + U * np.abs(dg)
-        c = dg * f.inv
-        ec = edg * f.inv + np.abs(dg) * f.einv + U * np.abs(c)
-        if flaw == "no_proj":
-            c = np.zeros_like(c)
-        t = dW - c[:, None] * f.v
-        et = edW + ec[:, None] * np.abs(f.v) + np.abs(c)[:, None] * f.ev + U * np.abs(c[:, None] * f.v) + U * np.abs(t)
-        dv = f.s[:, None] * t
-        grads[n + ".weight_g"] = dg.reshape(-1, 1)
-        k_grads[n + ".weight_g"] = LAMBDA * edg.reshape(-1, 1)
-        grads[n + ".weight_v"] = dv
-        k_grads[n + ".weight_v"] = LAMBDA * (f.es[:, None] * np.abs(t) + np.abs(f.s)[:, None] * et + U * np.abs(dv))
+        grads[n + ".weight_g"], k_grads[n + ".weight_g"], grads[n + ".weight_v"], k_grads[n + ".weight_v"] = weight_norm_backward(f, K, dW, edW, flaw)
         out.setdefault("dW", {})[n] = dW
+        if pieces:
+            out.setdefault("pieces", {})[n] = (D, eD, Xf, eXf)
         return dX, edX
 
     def through(L, dX, edX):
@@ -250,6 +256,8 @@ def run(head, params, z, sid, dcoef=None, dparams=None, flaw=None, slope=SLOPE32
     else:
         dz, edz = shares[0]
     out.update(dz=dz, k_dz=LAMBDA * edz, grads=grads, k_grads=k_grads, ambiguous=ambiguous)
+    if pieces:
+        out["fold"] = lay
     return out
 
 

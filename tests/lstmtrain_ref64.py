@@ -109,7 +109,7 @@ def _s_prime(s, e_s):
     return s * (1.0 - s), np.abs(1.0 - 2.0 * s) * e_s + 2 * U * s * (1.0 - s)
 
 
-def _direction(X, eX, Wih, eWih, Whh, eWhh, dY, edY, flaw):
+def _direction(X, eX, Wih, eWih, Whh, eWhh, dY, edY, flaw, pieces=False):
     """One direction over ASCENDING steps (the caller flips the reverse direction's time axis): sigmas in, sigmas out."""
     N, I = X.shape[0], X.shape[2]
     rows = N * TS
@@ -192,15 +192,18 @@ def _direction(X, eX, Wih, eWih, Whh, eWhh, dY, edY, flaw):
     out.update(dG=dG, e_dG=e_dG,
                dWih=Gf.T @ Xf, e_dWih=eGf.T @ np.abs(Xf) + aGf.T @ eXf + np.sqrt(rows + 1) * U * (aGf.T @ np.abs(Xf)),
                dWhh=Gf.T @ Hf, e_dWhh=eGf.T @ np.abs(Hf) + aGf.T @ eHf + np.sqrt(rows + 1) * U * (aGf.T @ np.abs(Hf)))
+    if pieces:
+        out["pieces"] = dict(dG=dG, e_dG=e_dG, X=X, e_X=eX, hprev=hprev, e_hprev=e_hprev)      # in this direction's step order
     return out
 
 
 _IFOG = np.r_[0:2 * NH, 3 * NH:4 * NH, 2 * NH:3 * NH]          # an involution of the gate rows
 
 
-def run(layer, params, X, dY=None, dparams=None, flaw=None, kX=None, kdY=None, want_dX=True):
+def run(layer, params, X, dY=None, dparams=None, flaw=None, kX=None, kdY=None, want_dX=True, pieces=False):
     """float32 inputs -> dict: Y, dX, grads {name: array} in float64 and their kappas k_Y, k_dX, k_grads; mean_f, the mean forget
-    gate.  dY None: forward only."""
+    gate.  dY None: forward only.  pieces: also `pieces`, per direction the operands of dW_ih and dW_hh (dG, X, h_{t-1} and their
+    sigmas, frame by frame; tests/bigbatch_ref64.py sums them with other frame weights)."""
     assert flaw is None or flaw in FLAWS, flaw
     X = _f64(X)
     N, I = X.shape[0], IN_DIM[layer]
@@ -220,7 +223,7 @@ def run(layer, params, X, dY=None, dparams=None, flaw=None, kX=None, kdY=None, w
         tr = (lambda a: a[:, ::-1]) if flip else (lambda a: a)
         sl = slice(d * NH, (d + 1) * NH)
         r = _direction(tr(X), tr(eX), W[d], eW[d], W[2 + d], eW[2 + d], None if dY is None else tr(dY[:, :, sl]),
-                       None if dY is None else tr(edY[:, :, sl]), flaw)
+                       None if dY is None else tr(edY[:, :, sl]), flaw, pieces)
         for k in ("h", "e_h", "gf", "dG", "e_dG"):
             if k in r:
                 r[k] = tr(r[k])
@@ -237,6 +240,8 @@ def run(layer, params, X, dY=None, dparams=None, flaw=None, kX=None, kdY=None, w
                 g, k = g[_IFOG], k[_IFOG]
             grads[n], kg[n] = g, k
     out.update(grads=grads, k_grads=kg)
+    if pieces:
+        out["pieces"] = [r["pieces"] for r in res]
     if want_dX:
         rows = N * TS
         G = [r["dG"].reshape(rows, NG) for r in res]

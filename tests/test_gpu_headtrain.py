@@ -6,8 +6,8 @@ fitted, and no constant factor is applied.
 
 Shapes.  N = 2: one pair, the smallest legal batch.  N = 100: the reference's batch; the 64-row tile is ragged (36 rows in the
 second one) and the dW contraction ends inside a chunk of 32 (100 = 3 x 32 + 4).  N = 2,050: 32 row tiles and a 2-row tail; the
-contraction over the rows is NOT split (one accumulator chain per tile, whatever N), so there is no partition boundary to
-cross.  P = 85, 180 and 59 leave ragged 64-column tiles; K = 520 = 8 x 64 + 8 leaves the one-hot columns and the column of
+contraction over the rows is one accumulator chain per tile up to 4,096 rows, so there is no partition boundary to cross here
+(tests/test_gpu_bigbatch_train.py crosses 64 of them at 262,146 rows).  P = 85, 180 and 59 leave ragged 64-column tiles; K = 520 = 8 x 64 + 8 leaves the one-hot columns and the column of
 ones that carries db in a ninth tile.  Both heads at each N; speaker 5 is absent from every case.
 
 Further: each wrong model of headtrain_ref64.FLAWS lies more than 100 x kappa from the device somewhere; Adam alone on
