@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "model.h"
 #include "../../include/sdfa_bilstm.h"
+#include "../../include/sdfa_freqtrain.h"
 
 #include <algorithm>
 
@@ -165,17 +166,19 @@ int sdfa_model_set_reserved_cus(sdfa_model *m, int k) {
 // ------------------------------------------------------------------------------------------------
 static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,
                         const int64_t *d_frame_start, int hop, float *d_z, float *d_align, float *d_H, void *d_workspace,
-                        int64_t workspace_bytes, void *stream, float *d_X1 = nullptr, float *d_X0 = nullptr) {
+                        int64_t workspace_bytes, void *stream, float *d_X1 = nullptr, float *d_X0 = nullptr, float *d_C = nullptr) {
     // d_H (sdfa_encoder_memory): every chunk's BiLSTM output leaves the K4 region as [n][64][512] before the next chunk reuses it;
     // d_z may then be null.  Null for every other entry point, which launch what they always launched.
     // d_X1 (sdfa_encoder_layer0): every chunk's layer-0 output leaves its K4 region the same way, and the chunk ends there: no
     // layer 1, no attention.  d_z, d_align and d_H are null then.
     // d_X0 (sdfa_encoder_x0): every chunk's frequency projection leaves its K4 region as [n][64][256], and the chunk ends there: no
     // BiLSTM.  The projection has to exist for every column then, so the chunk takes the expand-then-project order's first half.
+    // d_C (sdfa_encoder_conv): every chunk's conv-stack output leaves X3 as [n][64][32][64], through the share map where X3 holds the
+    // distinct columns only, and the chunk ends there: no frequency LSTM.
     if (!m || !m->finalized) return sdfa_fail(SDFA_ESTATE, "encoder_forward: model not finalised");
     if (n_frames == 0) return SDFA_OK;
-    if (!d_audio_feat || (!d_z && !d_H && !d_X1 && !d_X0) || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
-    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z | (uintptr_t)d_H | (uintptr_t)d_X1 | (uintptr_t)d_X0) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
+    if (!d_audio_feat || (!d_z && !d_H && !d_X1 && !d_X0 && !d_C) || !d_workspace || n_frames < 0) return sdfa_fail(SDFA_EINVAL, "encoder_forward: bad argument");
+    if (((uintptr_t)d_workspace | (uintptr_t)d_audio_feat | (uintptr_t)d_z | (uintptr_t)d_H | (uintptr_t)d_X1 | (uintptr_t)d_X0 | (uintptr_t)d_C) & 15) return sdfa_fail(SDFA_EINVAL, "encoder_forward: pointers must be 16-byte aligned");
     if ((uintptr_t)d_align & 3) return sdfa_fail(SDFA_EINVAL, "encoder_forward: d_align must be 4-byte aligned");
     const int64_t cap = capacity(workspace_bytes, m->keep);
     if (cap < 128) return sdfa_fail(SDFA_ENOSPACE, "encoder_forward: workspace of %lld bytes holds no 128-frame chunk", (long long)workspace_bytes);
@@ -243,6 +246,11 @@ static int encoder_impl(const sdfa_model *m, const float *d_audio_feat, int64_t 
         } else {
             ca.wb = m->cv_wb; ca.terms = conv_terms;      // the mixed-precision modes run the stack on bf16 MFMA too
             pf.begin("conv23"); HIP_TRY(sdfa_launch_conv123(ca, s)); pf.end();
+        }
+
+        if (d_C) {       // X3 holds the distinct columns on the shared path: col_to_u is null on the every-column path
+            HIP_TRY(sdfa_launch_conv_rows(ws + w.X3, col_to_u, N, Nc, d_C + f0 * (64 * 2048), s));
+            continue;
         }
 
         // launch form: the "freq_lstm_shape" option if set; else, for the fp32 kernel, what sdfa_model_autotune measured (the split-bf16
@@ -414,6 +422,13 @@ int sdfa_encoder_x0(const sdfa_model *m, const float *d_audio_feat, int64_t n_fr
                     int64_t workspace_bytes, void *stream) {
     if (!d_X0) return sdfa_fail(SDFA_EINVAL, "encoder_x0: null pointer");
     return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, nullptr, nullptr, nullptr, d_workspace, workspace_bytes, stream, nullptr, d_X0);
+}
+
+// include/sdfa_freqtrain.h: the frozen encoder up to and including the conv stack, every column's 32 x 64 features as rows
+int sdfa_encoder_conv(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, float *d_C, void *d_workspace,
+                      int64_t workspace_bytes, void *stream) {
+    if (!d_C) return sdfa_fail(SDFA_EINVAL, "encoder_conv: null pointer");
+    return encoder_impl(m, d_audio_feat, n_frames, nullptr, nullptr, 0, nullptr, nullptr, nullptr, d_workspace, workspace_bytes, stream, nullptr, nullptr, d_C);
 }
 
 int sdfa_encoder_forward_shared(const sdfa_model *m, const float *d_audio_feat, int64_t n_frames, const int32_t *d_frame_clip,

@@ -259,6 +259,8 @@ hipError_t sdfa_launch_share_prev(const ShareArgs &a, hipStream_t s);     // pre
 hipError_t sdfa_launch_expand_cols(const float *Zu, const int32_t *col_to_u, float *Z, int nquads, int64_t Mc, hipStream_t s);
 // the expanded frequency projection Z, K4 [64][Mc] with m = t*Nc+n  ->  rows [N][64 t][256] (sdfa_encoder_x0); Z and dst 16-byte aligned
 hipError_t sdfa_launch_x0_rows(const float *Z, int64_t N, int64_t Nc, float *dst, hipStream_t s);
+// the conv stack's output X3, K4 [512][Mc] with m = t*Nc+n (or the distinct column col_to_u[m])  ->  rows [N][64 t][32 f][64 ch] (sdfa_encoder_conv)
+hipError_t sdfa_launch_conv_rows(const float *X3, const int32_t *col_to_u, int64_t N, int64_t Nc, float *dst, hipStream_t s);
 
 // Tail of the shared-column frequency projection (gemm_tail.hip): columns [*q_lo, *q_hi) -- device scalars, multiples of 256 -- of
 //   D[p][q] = sum_k P[k][p] * Q[k][q] + bias[p]      fp32, K4 output, 256 rows, Q in the tile-major hidden-state layout, K = 8192,

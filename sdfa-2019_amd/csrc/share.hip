@@ -324,3 +324,26 @@ hipError_t sdfa_launch_x0_rows(const float *Z, int64_t N, int64_t Nc, float *dst
                        reinterpret_cast<float4 *>(dst));
     return hipGetLastError();
 }
+
+// sdfa_encoder_conv (include/sdfa_freqtrain.h): the conv stack's output X3, K4 [512 quads][Mc] with rows f*64 + ch  ->  rows
+// (n, 64 t, 32 f, 64 ch), what the frequency LSTM reads.  A column's 2,048 features are already in output order, so the copy is a
+// transpose of [quad][column].  On the shared-column path X3 holds a chunk's distinct columns only: column (t, n) is then read at
+// col_to_u[t*Nc + n], as expand_cols_kernel reads it; a null map is the every-column layout.  A block is one time step of four
+// frames, as in x0_rows_kernel: a thread moves one quad of each of eight 64-quad slices.
+namespace {
+__global__ void __launch_bounds__(256) conv_rows_kernel(const float4 *__restrict__ src, const int32_t *__restrict__ col_to_u, int64_t N, int64_t Nc,
+                                                        float4 *__restrict__ dst) {
+    const int t = (int)(blockIdx.x & 63);
+    const int64_t n = (int64_t)(blockIdx.x >> 6) * 4 + (threadIdx.x & 3);
+    if (n >= N) return;
+    const int64_t Mc = 64 * Nc, m = (int64_t)t * Nc + n, u = col_to_u ? col_to_u[m] : m;
+    for (int q = (int)(threadIdx.x >> 2); q < 512; q += 64) dst[(n * 64 + t) * 512 + q] = src[(int64_t)q * Mc + u];
+}
+}  // namespace
+
+hipError_t sdfa_launch_conv_rows(const float *X3, const int32_t *col_to_u, int64_t N, int64_t Nc, float *dst, hipStream_t s) {
+    if (N < 1 || N > Nc || (N + 3) / 4 * 64 > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(conv_rows_kernel, dim3((unsigned)((N + 3) / 4 * 64)), dim3(256), 0, s, reinterpret_cast<const float4 *>(X3), col_to_u, N, Nc,
+                       reinterpret_cast<float4 *>(dst));
+    return hipGetLastError();
+}

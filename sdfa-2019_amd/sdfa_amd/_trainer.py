@@ -1,4 +1,4 @@
-"""What the three GPU trainers (sdfa_amd.headtrain, attntrain, lstmtrain) share on the host: a handle of libsdfa_hip.so that owns
+"""What the GPU trainers (sdfa_amd.headtrain, attntrain, lstmtrain, freqtrain) share on the host: a handle of libsdfa_hip.so that owns
 parameters, gradients and the Adam state on the device (csrc/trainstate.h), read and written under the reference's tensor names,
 and the weak registry through which a custom op of sdfa_amd.ops finds its trainer.  A subclass names its symbol prefix and its
 tensors and supplies forward and backward; DESIGN.md section 20."""

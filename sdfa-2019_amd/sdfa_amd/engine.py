@@ -303,6 +303,23 @@ class Engine(FrontendOnly):
         check(lib.sdfa_encoder_x0(self._m, _ptr(audio_feat), n, _ptr(X0), _ptr(ws), ws.numel(), _stream()))
         return X0
 
+    def encoder_conv(self, audio_feat):
+        """C (n,64,32,64): the encoder up to and including the conv stack, row (n, t) the 32 frequency bins x 64 channels of column t
+        of frame n -- the input of sdfa_amd.freqtrain.FreqTrainer (sdfa_encoder_conv, include/sdfa_freqtrain.h); neither the frequency
+        LSTM nor anything after it is launched."""
+        from . import freqtrain  # noqa: F401  (binds the entry point)
+        assert audio_feat.is_cuda and audio_feat.dtype == torch.float32 and tuple(audio_feat.shape[1:]) == FEAT_SHAPE
+        audio_feat = audio_feat.contiguous()
+        n = audio_feat.shape[0]
+        Cout = torch.empty((n, 64, 32, 64), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return Cout
+        if self._autotune_pending and n >= self.AUTOTUNE_MIN_FRAMES:
+            self.autotune(n)
+        ws = self.workspace(n)
+        check(lib.sdfa_encoder_conv(self._m, _ptr(audio_feat), n, _ptr(Cout), _ptr(ws), ws.numel(), _stream()))
+        return Cout
+
     @staticmethod
     def check_speaker_ids(speaker_id):
         """Raises what the reference's one_hot scatter_ raises for an id outside [0, 8) (saber/nn/functions.py:375-378).

@@ -20,6 +20,9 @@ host through PyTorch-ROCm custom ops"; SURVEY.md section 8(b) names them).
     torch.ops.sdfa.encoder_x0(audio_feat, model)                                          -> X0 f32[N,64,256], the BiLSTM's input (the frequency projection as rows; no BiLSTM)
     torch.ops.sdfa.lstm_train(X, trainer_key)                                           -> Y f32[N,64,512] of an LstmTrainer's BiLSTM layer, X f32[N,64,256 | 512];
                                                                                              backward leaves the layer's gradients in the trainer, returns dX (or None)
+    torch.ops.sdfa.encoder_conv(audio_feat, model)                                        -> C f32[N,64,32,64], the conv stack's output as the frequency LSTM reads it (no frequency LSTM)
+    torch.ops.sdfa.freq_train(C, trainer_key)                                             -> X0 f32[N,64,256] of a FreqTrainer's frequency LSTM and projection;
+                                                                                             backward leaves their gradients in the trainer, returns dC (or None)
 
 Thin by design: each op is the matching `Engine` method (ctypes call into libsdfa_hip.so on the current stream), registered
 with the dispatcher through `torch.library.custom_op` and given a fake-tensor shape function, so the ops compose with
@@ -174,6 +177,17 @@ def encoder_x0(audio_feat: Tensor, model: str) -> Tensor:
 @encoder_x0.register_fake
 def _(audio_feat, model):
     return audio_feat.new_empty((audio_feat.shape[0], 64, 256))
+
+
+@custom_op("sdfa::encoder_conv", mutates_args=(), device_types="cuda")
+def encoder_conv(audio_feat: Tensor, model: str) -> Tensor:
+    """sdfa_encoder_conv: the encoder up to and including the conv stack, C [N][64][32][64], what the trained frequency LSTM reads."""
+    return _model(model).encoder_conv(audio_feat)
+
+
+@encoder_conv.register_fake
+def _(audio_feat, model):
+    return audio_feat.new_empty((audio_feat.shape[0], 64, 32, 64))
 
 
 @custom_op("sdfa::encoder_shared", mutates_args=(), device_types="cuda")
@@ -364,6 +378,35 @@ def _lstm_train_backward(ctx, grad_Y):
 
 
 lstm_train.register_autograd(_lstm_train_backward, setup_context=_lstm_train_setup)
+
+
+# --------------------------------------------------------------------------------------------------- frequency LSTM training
+@custom_op("sdfa::freq_train", mutates_args=(), device_types="cuda")
+def freq_train(C: Tensor, trainer_key: str) -> Tensor:
+    """sdfa_freqtrain_forward of the FreqTrainer registered as `trainer_key` (sdfa_amd.freqtrain.register_trainer): the training
+    forward of the frequency LSTM and its projection, C f32[N,64,32,64] -> X0 f32[N,64,256].  The parameters live in the trainer,
+    not in the graph: the backward needs C to require grad, runs sdfa_freqtrain_backward, OVERWRITES the trainer's parameter
+    gradients and returns dC -- or None (a null d_dC) unless the trainer has want_dC = True: the conv stack is frozen."""
+    from .freqtrain import trainer_of
+    return trainer_of(trainer_key).forward(C.contiguous())
+
+
+@freq_train.register_fake
+def _(C, trainer_key):
+    return C.new_empty((C.shape[0], 64, 256))
+
+
+def _freq_train_setup(ctx, inputs, output):
+    ctx.trainer_key = inputs[1]
+
+
+def _freq_train_backward(ctx, grad_X0):
+    from .freqtrain import trainer_of
+    tr = trainer_of(ctx.trainer_key)
+    return tr.backward(grad_X0.contiguous(), want_dC=getattr(tr, "want_dC", False)), None
+
+
+freq_train.register_autograd(_freq_train_backward, setup_context=_freq_train_setup)
 
 
 class TraceableSpeechDrivenAnimation(torch.nn.Module):

@@ -218,7 +218,7 @@ class SaberSpeechDrivenAnimation:
             raise NotImplementedError(f"head training: optim.args {sorted(unknown)} are not built")
         return dict(lr=float(args.get("lr", 1e-4)), betas=tuple(args.get("betas", (0.9, 0.999))), eps=float(args.get("eps", 1e-8)))
 
-    def enable_head_training(self, state_dict, attention=False, bilstm_top=False, bilstm_dropout=0.0, bilstm_bottom=False):
+    def enable_head_training(self, state_dict, attention=False, bilstm_top=False, bilstm_dropout=0.0, bilstm_bottom=False, freq_lstm=False):
         """Make the regressor head of `state_dict` (the one given to load_state_dict: weight_g / weight_v / bias under the
         reference's names) trainable on the device, with the encoder frozen: a sdfa_amd.headtrain.HeadTrainer with the
         reference's optimiser, and the PCA bases for get_loss.  The finalised inference engine stays read-only; commit_head()
@@ -237,8 +237,14 @@ class SaberSpeechDrivenAnimation:
 
         bilstm_bottom=True (with bilstm_top=True) also trains the bottom layer of the BiLSTM through a
         second LstmTrainer(layer=0): the frozen stack ends at the frequency projection (torch.ops.sdfa.encoder_x0), the top
-        layer's dX flows through the keep mask into the bottom layer's backward, and everything above the frequency LSTM trains."""
+        layer's dX flows through the keep mask into the bottom layer's backward, and everything above the frequency LSTM trains.
+
+        freq_lstm=True (with bilstm_bottom=True) also trains the frequency LSTM and its projection (layer 6 of the audio encoder;
+        DESIGN.md section 21) through a sdfa_amd.freqtrain.FreqTrainer: the frozen stack ends at the conv stack
+        (torch.ops.sdfa.encoder_conv), the bottom layer forms dX0, and everything above the conv stack trains."""
         from sdfa_amd.headtrain import HeadTrainer, register_trainer
+        if freq_lstm and not bilstm_bottom:
+            raise NotImplementedError("head training: freq_lstm=True needs bilstm_bottom=True: the frequency LSTM is trained through the bottom layer's dX")
         if bilstm_bottom and not bilstm_top:
             raise NotImplementedError("head training: bilstm_bottom=True needs bilstm_top=True: the bottom layer is trained through the top layer's dX")
         if bilstm_top and not attention:
@@ -256,9 +262,12 @@ class SaberSpeechDrivenAnimation:
         self._attn_trainer = self._attn_trainer_key = None
         self._lstm_trainer = self._lstm_trainer_key = None
         self._lstm0_trainer = self._lstm0_trainer_key = None
+        self._freq_trainer = self._freq_trainer_key = None
         self._bilstm_dropout = float(bilstm_dropout)
         self._train_flags = dict(attention=bool(attention), bilstm_top=bool(bilstm_top), bilstm_bottom=bool(bilstm_bottom),
                                  bilstm_dropout=float(bilstm_dropout))
+        if freq_lstm:
+            self._train_flags["freq_lstm"] = True      # the key exists only when set: a state taken without it has the flags it always had
         if attention:
             from sdfa_amd import attntrain
             # dH is consumed by the BiLSTM layer's backward, and by nothing without it
@@ -270,8 +279,13 @@ class SaberSpeechDrivenAnimation:
             self._lstm_trainer = lstmtrain.LstmTrainer(state_dict, layer=1, device=self._model._engine.device, want_dX=bool(bilstm_bottom), **optim)
             self._lstm_trainer_key = lstmtrain.register_trainer(self._lstm_trainer)
         if bilstm_bottom:
-            self._lstm0_trainer = lstmtrain.LstmTrainer(state_dict, layer=0, device=self._model._engine.device, want_dX=False, **optim)   # the frequency LSTM is frozen
+            # dX0 is consumed by the frequency LSTM's backward, and by nothing while it is frozen
+            self._lstm0_trainer = lstmtrain.LstmTrainer(state_dict, layer=0, device=self._model._engine.device, want_dX=bool(freq_lstm), **optim)
             self._lstm0_trainer_key = lstmtrain.register_trainer(self._lstm0_trainer)
+        if freq_lstm:
+            from sdfa_amd import freqtrain
+            self._freq_trainer = freqtrain.FreqTrainer(state_dict, device=self._model._engine.device, want_dC=False, **optim)   # the conv stack is frozen
+            self._freq_trainer_key = freqtrain.register_trainer(self._freq_trainer)
         return self
 
     def _bilstm_keep_mask(self, X1):
@@ -298,16 +312,24 @@ class SaberSpeechDrivenAnimation:
         the frozen stack ends at the layer-0 output (torch.ops.sdfa.encoder_layer0), times the keep mask where bilstm_dropout
         is set, and layer 1 of the BiLSTM runs through torch.ops.sdfa.lstm_train in front of the attention layer.  With
         bilstm_bottom=True the frozen stack ends at the BiLSTM's input (torch.ops.sdfa.encoder_x0) and both layers run through
-        torch.ops.sdfa.lstm_train, the keep mask between them inside the graph."""
+        torch.ops.sdfa.lstm_train, the keep mask between them inside the graph.  With freq_lstm=True the frozen stack ends at the
+        conv stack (torch.ops.sdfa.encoder_conv) and the frequency LSTM runs through torch.ops.sdfa.freq_train in front of them."""
         tr = self._trainer()
         self.train()
         if getattr(self, "_lstm0_trainer", None) is not None:
             # both BiLSTM layers + attention + head: dH flows into layer 1's backward, its dX1 through the keep mask (autograd's
             # product rule: nn.LSTM's inter-layer dropout with both layers trained) into layer 0's; the frequency LSTM and
             # everything below are frozen, so no dX0 is formed
-            with torch.no_grad():
-                X0 = torch.ops.sdfa.encoder_x0(batch["audio_feat"].contiguous(), self._model._key)
-            X0 = X0.detach().requires_grad_(True)
+            if getattr(self, "_freq_trainer", None) is not None:
+                # the frequency LSTM as well: layer 0's dX0 flows into its backward; the conv stack is frozen, so no dC is formed
+                with torch.no_grad():
+                    Cx = torch.ops.sdfa.encoder_conv(batch["audio_feat"].contiguous(), self._model._key)
+                Cx = Cx.detach().requires_grad_(True)
+                X0 = torch.ops.sdfa.freq_train(Cx, self._freq_trainer_key)
+            else:
+                with torch.no_grad():
+                    X0 = torch.ops.sdfa.encoder_x0(batch["audio_feat"].contiguous(), self._model._key)
+                X0 = X0.detach().requires_grad_(True)
             X1 = torch.ops.sdfa.lstm_train(X0, self._lstm0_trainer_key)
             if self._bilstm_dropout > 0.0:
                 with torch.no_grad():
@@ -355,6 +377,9 @@ class SaberSpeechDrivenAnimation:
             raise RuntimeError(f"head trainer at step {tr.step_count}, BiLSTM trainer at step {lt.step_count}: they step together")
         if l0 is not None and l0.step_count != tr.step_count:
             raise RuntimeError(f"head trainer at step {tr.step_count}, BiLSTM bottom-layer trainer at step {l0.step_count}: they step together")
+        fq = getattr(self, "_freq_trainer", None)
+        if fq is not None and fq.step_count != tr.step_count:
+            raise RuntimeError(f"head trainer at step {tr.step_count}, frequency-LSTM trainer at step {fq.step_count}: they step together")
         tr.step()
         if at is not None:
             at.step()
@@ -362,6 +387,8 @@ class SaberSpeechDrivenAnimation:
             lt.step()
         if l0 is not None:
             l0.step()
+        if fq is not None:
+            fq.step()
 
     def fit_head(self, trainset, steps, rng, batch_size=50, noise="device", fixed_batch=None):
         """`steps` steps of the reference's loop (trainer.py:266-320: train_step, the summed losses' backward, optim.step) over
@@ -384,7 +411,8 @@ class SaberSpeechDrivenAnimation:
         """The tuned head under the reference's names ("_model._output_module. ... weight_g | weight_v | bias"), and with
         attention training enabled the tuned attention tensors ("_model._audio_encoder._layers.10. ..."), with bilstm_top the
         four tuned layer-1 tensors of the BiLSTM ("_model._audio_encoder._layers.9.weight_ih_l1 ..."), with bilstm_bottom the
-        four layer-0 tensors ("... weight_ih_l0", "weight_hh_l0" and their "_reverse" twins)."""
+        four layer-0 tensors ("... weight_ih_l0", "weight_hh_l0" and their "_reverse" twins), with freq_lstm the ten tensors of
+        the frequency LSTM and its projection ("_model._audio_encoder._layers.6._lstm. ...", "..._proj.weight | bias")."""
         tuned = self._trainer().head_state_dict()
         if getattr(self, "_attn_trainer", None) is not None:
             tuned.update(self._attn_trainer.attn_state_dict())
@@ -392,14 +420,17 @@ class SaberSpeechDrivenAnimation:
             tuned.update(self._lstm_trainer.lstm_state_dict())
         if getattr(self, "_lstm0_trainer", None) is not None:
             tuned.update(self._lstm0_trainer.lstm_state_dict())
+        if getattr(self, "_freq_trainer", None) is not None:
+            tuned.update(self._freq_trainer.freq_state_dict())
         return tuned
 
     # ---- save, stop, resume: what a training loop around train_step has to carry ----
-    _TRAINER_SLOTS = (("head", "_head_trainer"), ("attention", "_attn_trainer"), ("bilstm_top", "_lstm_trainer"), ("bilstm_bottom", "_lstm0_trainer"))
+    _TRAINER_SLOTS = (("head", "_head_trainer"), ("attention", "_attn_trainer"), ("bilstm_top", "_lstm_trainer"), ("bilstm_bottom", "_lstm0_trainer"),
+                      ("freq_lstm", "_freq_trainer"))
 
     def training_state_dict(self):
         """Everything a fit needs to continue bit for bit: every enabled trainer's state_dict() (parameters, both Adam moments,
-        the step count, the optimiser arguments) under "head", "attention", "bilstm_top", "bilstm_bottom"; the
+        the step count, the optimiser arguments) under "head", "attention", "bilstm_top", "bilstm_bottom", "freq_lstm"; the
         DynamicLossScalers' state by the reference's names; the dropout generator's state (None while nothing has been drawn);
         and the flags enable_head_training was called with.  Host data only, so torch.save takes it."""
         self._trainer()
@@ -414,7 +445,9 @@ class SaberSpeechDrivenAnimation:
         by name, before anything is changed."""
         self._trainer()
         theirs, mine = dict(state["flags"]), self._train_flags
-        differ = [f"{k}={theirs.get(k)!r} (this model: {k}={mine[k]!r})" for k in mine if theirs.get(k) != mine[k]]
+        differ = [f"{k}={theirs.get(k)!r} (this model: {k}={mine[k]!r})" for k in mine if k != "freq_lstm" and theirs.get(k) != mine[k]]
+        if bool(theirs.get("freq_lstm", False)) != bool(mine.get("freq_lstm", False)):      # a key that exists only when set
+            differ.append(f"freq_lstm={bool(theirs.get('freq_lstm', False))!r} (this model: freq_lstm={bool(mine.get('freq_lstm', False))!r})")
         if differ or set(theirs) != set(mine):
             raise ValueError("training state: taken with " + ", ".join(differ or sorted(set(theirs) ^ set(mine))) +
                              ": enable_head_training must be called with the flags the state was taken with")

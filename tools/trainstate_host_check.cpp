@@ -1,14 +1,15 @@
 // Host-only check of the training handles' shared core (sdfa-2019_amd/csrc/trainstate.h), which frees and copies: without a device,
-// for each of sdfa_headtrain, sdfa_attntrain and sdfa_lstmtrain: create, set_tensor (good name, bad name, short numel, null
+// for each of sdfa_headtrain, sdfa_attntrain, sdfa_lstmtrain and sdfa_freqtrain: create, set_tensor (good name, bad name, short numel, null
 // data), the finalize-with-a-missing-tensor refusal, the calls an unfinalised handle refuses, and destroy of the unfinalised handle.
 // Meant to run under AddressSanitizer and UBSan on the host side only, from sdfa-2019_amd/csrc:
 //
 //   hipcc -std=c++17 --offload-arch=gfx950 -g -O1 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
 //       -x hip ../../tools/trainstate_host_check.cpp api_core.cpp api_headtrain.cpp api_attntrain.cpp api_lstmtrain.cpp \
-//       headtrain.hip attntrain.hip lstmtrain.hip -o trainstate_host_check && ./trainstate_host_check
+//       api_freqtrain.cpp headtrain.hip attntrain.hip lstmtrain.hip freqtrain.hip -o trainstate_host_check && ./trainstate_host_check
 //
 // It launches nothing; exit status 0 and "trainstate host check: ok" is a pass, a sanitizer report is a failure.
 #include "../include/sdfa_attntrain.h"
+#include "../include/sdfa_freqtrain.h"
 #include "../include/sdfa_headtrain.h"
 #include "../include/sdfa_hip.h"
 #include "../include/sdfa_lstmtrain.h"
@@ -107,10 +108,27 @@ int main() {
          {{"_audio_encoder._layers.9.weight_ih_l0", 1024 * 256}, {"_audio_encoder._layers.9.weight_ih_l0_reverse", 1024 * 256}, {"_audio_encoder._layers.9.weight_hh_l0_reverse", 1024 * 256}}},
         {"lstmtrain layer 1", API(lstmtrain, sdfa_lstmtrain_create(512)),
          {{"_audio_encoder._layers.9.weight_ih_l1", 1024 * 512}, {"_audio_encoder._layers.9.weight_ih_l1_reverse", 1024 * 512}, {"_audio_encoder._layers.9.weight_hh_l1_reverse", 1024 * 256}}},
+        {"freqtrain", API(freqtrain, sdfa_freqtrain_create()),
+         {{"_audio_encoder._layers.6._lstm.weight_ih_l0", 512 * 64}, {"_audio_encoder._layers.6._lstm.weight_ih_l0_reverse", 512 * 64}, {"_audio_encoder._layers.6._proj.bias", 256}}},
     };
     for (const Api &a : apis) run(a);
     expect("headtrain_create(7)", sdfa_headtrain_create(7) ? 0 : -1, -1, "unknown head");
     expect("lstmtrain_create(384)", sdfa_lstmtrain_create(384) ? 0 : -1, -1, "input width");
+    // the frequency-LSTM handle's own calls: the step and the encoder exit refuse before they look at a device
+    {
+        sdfa_freqtrain *h = sdfa_freqtrain_create();
+        std::vector<float> wp((size_t)256 * 8192, 0.5f);            // the largest tensor of any handle, copied whole
+        expect("freqtrain: set_tensor, _proj.weight", sdfa_freqtrain_set_tensor(h, "_audio_encoder._layers.6._proj.weight", wp.data(), (int64_t)wp.size()), SDFA_OK, nullptr);
+        expect("freqtrain: set_tensor, the BiLSTM's name", sdfa_freqtrain_set_tensor(h, "_audio_encoder._layers.9.weight_hh_l0", wp.data(), 1024 * 256), SDFA_EINVAL,
+               "the frequency LSTM has no tensor");
+        expect("freqtrain: forward, unfinalised", sdfa_freqtrain_forward(h, nullptr, 1, nullptr, nullptr, 0, nullptr), SDFA_ESTATE, "not finalised");
+        expect("freqtrain: backward, unfinalised", sdfa_freqtrain_backward(h, nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr), SDFA_ESTATE, "not finalised");
+        expect("freqtrain: workspace_bytes(0)", sdfa_freqtrain_workspace_bytes(h, 0), SDFA_EINVAL, "frames outside");
+        expect("freqtrain: workspace_bytes(MAX + 1)", sdfa_freqtrain_workspace_bytes(h, SDFA_FREQTRAIN_MAX_FRAMES + 1), SDFA_EINVAL, "frames outside");
+        expect("freqtrain: workspace_bytes(MAX) > 2^34", sdfa_freqtrain_workspace_bytes(h, SDFA_FREQTRAIN_MAX_FRAMES) > ((int64_t)1 << 34), 1, nullptr);
+        sdfa_freqtrain_destroy(h);                                      // before finalize
+        expect("freqtrain: forward, null handle", sdfa_freqtrain_forward(nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr), SDFA_EINVAL, "null handle");
+    }
     printf(failures ? "trainstate host check: %d UNEXPECTED\n" : "trainstate host check: ok\n", failures);
     return failures ? 1 : 0;
 }
