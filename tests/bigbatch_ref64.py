@@ -1,5 +1,5 @@
 """The float64 value of a training step on a PERIODIC batch, however large, from the float64 models of a few frames: what lets
-tests/test_gpu_bigbatch_train.py hold the three GPU trainers to float64 at the largest batches their headers accept.
+tests/test_gpu_bigbatch_train.py hold the four GPU trainers to float64 at the largest batches their headers accept.
 
 The batch.  A pool of POOL = 7 distinct frames (rows, for the head) comes from the ref module's own case(...).  Frame n of the large
 batch is pool frame j_n and its incoming gradient is 2^{k_n} times pool gradient j_n, j_n in 0 .. 6 and k_n in {-1, 0, 1} from a
@@ -12,7 +12,8 @@ gradient is sum_j A_j (frame j's own gradient), and the ref modules' per-frame o
 exactly.  kappa follows the modules' own rules and nothing else: errors that come in over the rows add linearly, so the
 first-order part is sum_j |A_j| times frame j's, and the summation part is the modules' "n products summed in ANY order",
 sqrt(R + 1) U sum_j |A_j| |a|^T |b|_j with R the number of summed rows that are not exactly zero -- frames kept times 64 for the
-contractions over (n, t), frames kept for those over n (the attention layer's dWq and dWc, the head).  Every sigma of a backward
+contractions over (n, t), frames kept for those over n (the attention layer's dWq and dWc, the head), frames kept times 2,048 for
+the frequency LSTM's contractions over (column, step), whose frame is 64 columns.  Every sigma of a backward
 is homogeneous of degree one in the incoming gradient, so the weights carry through.  One Adam step is headtrain_ref64.adam.
 
 tests/test_bigbatch_ref64_cpu.py pins all of this against the modules' plain run on a materialised batch.
@@ -24,6 +25,7 @@ is a few percent of a frame's own gradient), the set is run as several interleav
 import numpy as np
 
 import attntrain_ref64 as AT
+import freqtrain_ref64 as FT
 import headtrain_ref64 as HD
 import lstmtrain_ref64 as LS
 from headtrain_ref64 import LAMBDA, U, adam
@@ -243,6 +245,38 @@ def head_periodic(head, params, z_pool, sid_pool, dcoef_pool, j, k, keep=None, A
     return _result(pool, grads, kg, A, frames, step)
 
 
+# ---------------------------------------------------------------------------------------------------- the frequency LSTM
+def freq_pool(params, C_pool, dX0_pool):
+    """the pool's float64 run (X0, dC and their kappas per frame) and its per-frame tables.  A frame is 64 columns: C_pool
+    [POOL 64][32][64], dX0_pool [POOL 64][256].  dWp and dbp sum over the columns, 64 rows a frame; dW_ih, dW_hh and the bias
+    gradient over the pairs (column, step), 2,048 rows a frame.  bias_ih and bias_hh of a direction share one table (the same
+    gradient) and each takes its own Adam step."""
+    assert len(C_pool) == len(dX0_pool) == POOL * FT.COLS
+    r = FT.run(params, C_pool, dX0_pool, pieces=True)
+    p = r.pop("pieces")
+    nm = FT.names()
+    cols = lambda x: x.reshape(POOL, FT.COLS, -1)
+    pairs = lambda x: x.reshape(POOL, FT.COLS * FT.NS, -1)
+    tables = {
+        nm[8]: _table(cols(p["D"]), cols(p["e_D"]), cols(p["HF"]), cols(p["e_HF"]), FT.COLS),
+        nm[9]: _table(cols(p["D"]), cols(p["e_D"]), np.ones((POOL, FT.COLS, 1)), None, FT.COLS, lambda x: x[:, 0]),
+    }
+    ones = np.ones((POOL, FT.COLS * FT.NS, 1))
+    for d, q in enumerate(p["dirs"]):
+        dG, e_dG = pairs(q["dG"]), pairs(q["e_dG"])
+        tables[nm[d]] = _table(dG, e_dG, pairs(q["Cf"]), pairs(q["eCf"]), FT.COLS * FT.NS)
+        tables[nm[2 + d]] = _table(dG, e_dG, pairs(q["hprev"]), pairs(q["e_hprev"]), FT.COLS * FT.NS)
+        tables[nm[4 + d]] = tables[nm[6 + d]] = _table(dG, e_dG, ones, None, FT.COLS * FT.NS, lambda x: x[:, 0])
+    for n, shape in (("X0", (FT.COLS, FT.NO)), ("dC", (FT.COLS, FT.NS, FT.NI))):
+        r[n], r["k_" + n] = r[n].reshape((POOL,) + shape), r["k_" + n].reshape((POOL,) + shape)
+    return dict(run=r, params=params, tables=tables)
+
+
+def freq_periodic(params, C_pool, dX0_pool, j, k, keep=None, A=None, frames=None, pool=None, step=True):
+    """as lstm_periodic, for the frequency LSTM and its projection"""
+    return _plain(pool or freq_pool(params, C_pool, dX0_pool), j, k, keep, A, frames, step)
+
+
 # ---------------------------------------------------------------------------------------------------- the cases
 # What tests/test_gpu_bigbatch_train.py runs and tests/test_bigbatch_ref64_cpu.py pins, per trainer variant.  N: the batches.
 # tile / block: frames (rows) of a recurrence tile (row tile) and of a row block of the split dW contractions; S_blocks takes one
@@ -257,6 +291,12 @@ VARIANTS = {
     "attn": dict(N=(32768, 32761), tile=16, block=16, every=32, off=2048, pool_seed=902, dense_tiles=216, groups=1),
     "head-dgrad": dict(N=(2 ** 18 + 2,), tile=64, block=64, every=64, off=2 ** 16, pool_seed=720, dense_tiles=11, groups=1),
     "head-offsets": dict(N=(2 ** 18 + 2,), tile=64, block=64, every=64, off=2 ** 16, pool_seed=727, dense_tiles=10, groups=1),
+    # the frequency LSTM: a frame is 64 columns, the periodic unit a frame (two recurrence tiles per direction), a row block 8 frames;
+    # 1,024 frames are 2^31 gate floats, the distance at which a 32-bit gate index would alias.  Measured: the last 4 frames lost or
+    # counted twice lie 10.5 x kappa away at N = 2,048 and 47.3 x at 1,033 (3 frames: 9.05 x and 36.4 x; 1 frame: 5.76 x and 15.3 x),
+    # on dbp, whose kappa is 2e-4 of the gradient; dW_ih, dW_hh and db (kappa 2 - 26 % of the gradient) do not see them (0.7 - 2.8 x).
+    # S_blocks in ONE pass of 256 / 130 frames: the best-seen frame lost lies 134 / 322 x away, a frame read from 1,024 earlier 113 / 130 x
+    "freq": dict(N=(2048, 1033), tile=1, block=8, every=1, off=1024, pool_seed=740, dense_tiles=4, groups=1),
 }
 _POOLS = {}
 
@@ -270,6 +310,8 @@ def pool_case(variant):
         return LS.case(int(which[1]), POOL, seed, "carry")
     if kind == "attn":
         return AT.case(POOL, seed, "peaked")
+    if kind == "freq":
+        return FT.case(FT.COLS * POOL, seed, "carry")
     return HD.case(which, (POOL + 1) // 2, seed)
 
 
@@ -282,6 +324,8 @@ def pool_of(variant):
             _POOLS[variant] = lstm_pool(c["layer"], c["params"], c["X"], c["dY"])
         elif kind == "attn":
             _POOLS[variant] = attn_pool(c["params"], c["H"], c["dz"])
+        elif kind == "freq":
+            _POOLS[variant] = freq_pool(c["params"], c["C"], c["dX0"])
         else:
             _POOLS[variant] = head_pool(c["head"], c["params"], c["z"][:POOL], c["sid"][:POOL], c["dcoef"][:POOL])
     return _POOLS[variant]

@@ -156,15 +156,19 @@ def _backward_direction(k, Whh, eWhh, dY, edY, flaw):
     Hf, eHf = hprev.reshape(pairs, NH), e_hprev.reshape(pairs, NH)
     Cf, eCf = k["Cf"], k["eCf"]
     s = np.sqrt(pairs + 1) * U
-    return dict(dG=dG, e_dG=e_dG,
+    return dict(dG=dG, e_dG=e_dG, hprev=hprev, e_hprev=e_hprev,
                 dWih=Gf.T @ Cf, e_dWih=eGf.T @ np.abs(Cf) + _mm(aGf.T, eCf) + s * (aGf.T @ np.abs(Cf)),
                 dWhh=Gf.T @ Hf, e_dWhh=eGf.T @ np.abs(Hf) + aGf.T @ eHf + s * (aGf.T @ np.abs(Hf)),
                 db=Gf.sum(0), e_db=eGf.sum(0) + s * aGf.sum(0))
 
 
-def run(params, C, dX0=None, dparams=None, flaw=None, kC=None, kdX0=None, want_dC=True):
+def run(params, C, dX0=None, dparams=None, flaw=None, kC=None, kdX0=None, want_dC=True, pieces=False):
     """float32 inputs -> dict: X0, HF, dC, grads {name: array} in float64 and their kappas k_X0, k_HF, k_dC, k_grads; mean_f, the
-    mean forget gate.  dX0 None: forward only.  kC, kdX0: kappas of C and dX0 where they are another stage's outputs."""
+    mean forget gate.  dX0 None: forward only.  kC, kdX0: kappas of C and dX0 where they are another stage's outputs.
+    pieces=True adds "pieces": the per-column operands of every contraction over the rows and their sigmas, the very arrays
+    contracted here (tests/bigbatch_ref64.py builds a periodic batch's gradients from them): D = dX0 [R][256] and HF [R][8192] with
+    e_D, e_HF for dWp and dbp; "dirs", per direction dG [R][32][512] (in the direction's own ascending step order, as contracted),
+    Cf [32 R][64] and hprev [R][32][128] with e_dG, eCf, e_hprev for dW_ih, dW_hh and db."""
     assert flaw is None or flaw in FLAWS, flaw
     C = _f64(C)
     R = C.shape[0]
@@ -211,8 +215,9 @@ def run(params, C, dX0=None, dparams=None, flaw=None, kC=None, kdX0=None, want_d
     for d in (0, 1):
         k, tr = res[d]
         r = _backward_direction(k, W[2 + d], eW[2 + d], tr(dHF[:, :, d]), tr(e_dHF[:, :, d]), flaw)
+        own = dict(dG=r["dG"], e_dG=r["e_dG"], Cf=k["Cf"], eCf=k["eCf"], hprev=r["hprev"], e_hprev=r["e_hprev"])
         r["dG"], r["e_dG"] = tr(r["dG"]), tr(r["e_dG"])
-        back.append(r)
+        back.append((r, own))
         grads[nm[d]], kg[nm[d]] = r["dWih"], LAMBDA * r["e_dWih"]
         grads[nm[2 + d]], kg[nm[2 + d]] = r["dWhh"], LAMBDA * r["e_dWhh"]
         grads[nm[4 + d]], kg[nm[4 + d]] = r["db"], LAMBDA * r["e_db"]
@@ -220,13 +225,15 @@ def run(params, C, dX0=None, dparams=None, flaw=None, kC=None, kdX0=None, want_d
     out.update(grads=grads, k_grads=kg, dHF=dHF.reshape(R, NK), k_dHF=LAMBDA * e_dHF.reshape(R, NK))
     if want_dC:
         pairs = R * NS
-        G = [r["dG"].reshape(pairs, NG) for r in back]
-        eG = [r["e_dG"].reshape(pairs, NG) for r in back]
+        G = [r["dG"].reshape(pairs, NG) for r, _ in back]
+        eG = [r["e_dG"].reshape(pairs, NG) for r, _ in back]
         use = (0,) if flaw == "dc_forward_only" else (0, 1)
         dC = sum(G[d] @ W[d] for d in use)
         q = sum((eG[d] * eG[d]) @ (W[d] * W[d]) + _mm(G[d] * G[d], eW[d] * eW[d]) for d in (0, 1))
         e_dC = np.sqrt(q + (np.sqrt(2 * NG + 1) * U * (np.abs(G[0]) @ np.abs(W[0]) + np.abs(G[1]) @ np.abs(W[1]))) ** 2)
         out.update(dC=dC.reshape(R, NS, NI), k_dC=LAMBDA * e_dC.reshape(R, NS, NI))
+    if pieces:
+        out["pieces"] = dict(D=D, e_D=eD, HF=HF, e_HF=eHF, dirs=[own for _, own in back])
     return out
 
 

@@ -1,7 +1,8 @@
 """tests/bigbatch_ref64.py pinned before any GPU is involved: the float64 value and kappa of a training step on a periodic batch,
 built from the pool's per-frame operands, against the ref modules' plain run on the same batch written out frame by frame.
 
-    the periodic model is the plain run     N = 14 (and 15 for the BiLSTM layer and the attention layer): every gradient within 1e-12
+    the periodic model is the plain run     N = 14 (and 15 for the BiLSTM layer and the attention layer, 17 for the frequency LSTM:
+                                            two whole row blocks and a frame): every gradient within 1e-12
                                             of the array's largest magnitude (both are float64 sums of the same terms in another
                                             order, whose difference is bounded by the terms, not by an element that cancels), every
                                             kappa within 1e-12 relative, with R the written-out batch's row count; the Adam step is
@@ -25,16 +26,23 @@ and 2.6e4 - 2.9e4 x for the head (65 rows): the BiLSTM's S_blocks is therefore r
 passes of 16 and 7 - 8 frames, the smallest numbers at which the two controls of every pass lie 10 x kappa away at both N.  Over all
 frames of S_blocks the loss of one lies 2.4 - 31 x kappa from its pass's model (BiLSTM), 0.07 - 16 x (attention; a pool frame whose
 largest align is 0.98 has next to no gradient: no gradient check resolves such a frame, the bit comparison of its dH does),
-3.8e3 - 2.9e4 x (head).  The module takes 28 s."""
+3.8e3 - 2.9e4 x (head).  The frequency LSTM (a frame is 64 columns; N = 2,048 and 1,033): its dbp and dWp sum exact incoming
+gradients, their kappa is 2e-4 and 9e-4 of the gradient, and the last 4 frames lost or counted twice lie 10.5 x (N = 2,048) and 47.3 x
+(1,033) away (3 frames 9.05 x and 36.4 x), while dW_ih, dW_hh and db, whose kappa is 2 - 26 % of the gradient, see them at 0.7 - 2.8 x
+only; S_blocks runs as ONE pass of 256 and 130 frames, in which the best-seen frame's loss lies 134 and 322 x away and its misreading
+from 1,024 frames earlier 113 and 130 x; over all its frames a loss lies 31.9 - 322 x away.  The module takes 60 s, 32 s of them
+the frequency LSTM's float64 runs."""
 import numpy as np
 import pytest
 
 import attntrain_ref64 as AT
 import bigbatch_ref64 as BB
+import freqtrain_ref64 as FT
 import headtrain_ref64 as HD
 import lstmtrain_ref64 as LS
 
-SMALL = [(v, N) for v in BB.VARIANTS for N in ((14,) if v.startswith("head") else (14, 15))]
+# the frequency LSTM's float64 run takes seconds per 576 columns: its written-out batches are 14 frames and 17 (two whole row blocks and a frame)
+SMALL = [(v, N) for v in BB.VARIANTS for N in ((14,) if v.startswith("head") else (14, 17) if v == "freq" else (14, 15))]
 LARGE = [(v, N) for v, d in BB.VARIANTS.items() for N in d["N"]]
 ids = lambda cases: [f"{v}-N{n}" for v, n in cases]
 
@@ -47,6 +55,12 @@ def plain(variant, frames, w):
         return LS.run(c["layer"], c["params"], c["X"][frames], (c["dY"][frames] * w[:, None, None]).astype(f32))
     if variant == "attn":
         return AT.run(c["params"], c["H"][frames], (c["dz"][frames] * w[:, None]).astype(f32))
+    if variant == "freq":
+        C4, dX3 = c["C"].reshape(BB.POOL, FT.COLS, FT.NS, FT.NI), c["dX0"].reshape(BB.POOL, FT.COLS, FT.NO)
+        r = FT.run(c["params"], C4[frames].reshape(-1, FT.NS, FT.NI), (dX3[frames] * w[:, None, None]).astype(f32).reshape(-1, FT.NO))
+        for n in ("X0", "k_X0", "dC", "k_dC"):                  # per frame, as the pool's
+            r[n] = r[n].reshape((len(frames), FT.COLS) + r[n].shape[1:])
+        return r
     return HD.run(c["head"], c["params"], c["z"][frames], c["sid"][frames], (c["dcoef"][frames] * w[:, None]).astype(f32))
 
 
@@ -57,11 +71,13 @@ def periodic(variant, j, k, keep=None):
         return BB.lstm_periodic(c["layer"], c["params"], c["X"], c["dY"], j, k, keep, pool=pool)
     if variant == "attn":
         return BB.attn_periodic(c["params"], c["H"], c["dz"], j, k, keep, pool=pool)
+    if variant == "freq":
+        return BB.freq_periodic(c["params"], c["C"], c["dX0"], j, k, keep, pool=pool)
     P = BB.POOL
     return BB.head_periodic(c["head"], c["params"], c["z"][:P], c["sid"][:P], c["dcoef"][:P], j, k, keep, pool=pool)
 
 
-OUT = {"lstm": ("Y", "dX"), "attn": ("z", "align", "dH"), "head": ("coef", "dz")}          # forward outputs first, dX / dH / dz last
+OUT = {"lstm": ("Y", "dX"), "attn": ("z", "align", "dH"), "head": ("coef", "dz"), "freq": ("X0", "dC")}          # forward outputs first, dX / dH / dz last
 
 
 def same(variant, per, ref):

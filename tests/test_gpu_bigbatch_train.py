@@ -1,9 +1,22 @@
-"""The three GPU trainers at the largest batches their headers accept, against float64: one BiLSTM layer (csrc/lstmtrain.hip) at
+"""The four GPU trainers at the largest batches their headers accept, against float64: one BiLSTM layer (csrc/lstmtrain.hip) at
 N = 3,072 = SDFA_LSTMTRAIN_MAX_FRAMES (96 whole recurrence tiles and row blocks) and 3,041 (95 whole plus one frame), layers 0 and 1,
 family "carry"; the attention layer (csrc/attntrain.hip) at N = 32,768 = SDFA_ATTNTRAIN_MAX_FRAMES and 32,761 (2,047 row blocks plus
 9 frames), family "peaked"; both heads (csrc/headtrain.hip) at N = 2^18 + 2 = 262,146 rows (4,096 whole row tiles and a 2-row
 tail).  THE HEAD IS NOT EXERCISED BETWEEN 262,146 ROWS AND ITS LIMIT OF 2^21: at 2^21 rows the dgrad head's workspace alone is 36 GiB,
-which is not something to hold on a shared card.  Every case holds less than 12 GiB on the device and asserts so.
+which is not something to hold on a shared card.  Every case of these three holds less than 12 GiB on the device and asserts so.
+
+The frequency LSTM and its projection (csrc/freqtrain.hip), family "carry", at N = 2,048 = SDFA_FREQTRAIN_MAX_FRAMES -- 256 whole
+row blocks of 8 frames, 256 partials in the reduce, 2^17 columns, the last gate float at index 2^32 - 1 and the second direction's
+gates exactly 2^31 floats behind the first's -- and at N = 1,033: 129 whole row blocks and one of a single frame (64 of 512 columns,
+both recurrences' grids ending inside a block), just past the 1,024 frames at which the gate offsets cross 2^31.  A frame is 64
+columns; the periodic unit is a frame (tile = 1), a row block 8 frames, a misread frame comes from 1,024 frames earlier, where a
+32-bit gate index would alias.  This trainer keeps 14 MiB per frame: its workspace is 30.2 GiB at 2,048 frames, and with C and dC
+(1 GiB each), X0, dX0 and the sparse dX0 (0.125 GiB each) and the comparison slices a case holds 33.1 GiB (asserted below 34 GiB;
+16.9 GiB, below 18, at N = 1,033).  That is acceptable where the head's 36 GiB was not because it is what ONE train_step at the
+header's limit holds in use and what the committed benchmark (tools/freqtrain_bench.py, profiles/freqtrain_bench.json) already held;
+the head's 36 GiB lie beyond any batch its training loop forms.  Everything is freed between cases; the bit comparisons run on the
+device in slices of 256 frames (a slice of the expected dC and its scaled copy: 256 MiB), and nothing of the batch's size goes to
+the host.
 
 The float64 models cannot be run at these sizes, so the batch is periodic (tests/bigbatch_ref64.py, pinned on the CPU by
 tests/test_bigbatch_ref64_cpu.py): frame n is one of 7 pool frames, j_n, with its incoming gradient times 2^{k_n}, built on the
@@ -48,21 +61,42 @@ left out as tiny.  The device lies 10.0 - 10.3 x kappa from the dense controls a
 2.6e4 - 2.9e4 x (head) from the S_blocks controls.  Held on the device: 4.0 / 4.8 GiB (BiLSTM layer 0 / 1), 11.6 GiB (attention), 6.6 / 3.3
 GiB (heads).  Broken copies of the library turn it red: a reduce that stops one block early only at large batches, and a products
 kernel that reads the row block before its own for blk >= 64, pass the dense pass and fail the S_edges gradients at 2.6 - 22 x kappa
-(BiLSTM, attention) and 163 - 4.6e3 x (head).  A case takes 0.3 - 2.6 s (the first of a variant makes its float64 pool model), the module 11 s."""
+(BiLSTM, attention) and 163 - 4.6e3 x (head).  A case takes 0.3 - 2.6 s (the first of a variant makes its float64 pool model), the module 11 s.
+
+The frequency LSTM, measured on an MI355X.  IT STAYS INSIDE KAPPA AT 2,048 FRAMES; nothing in csrc/freqtrain.hip was changed.  Largest
+|gpu - ref64| / kappa: the pool 0.0053 (X0), 0.0024 (dC), 0.070 (a gradient); dense gradients 0.0044 (N = 2,048) and 0.0049 (1,033);
+sparse passes 0.0166 and 0.0140 (S_edges), 0.0206 and 0.0156 (S_blocks, one pass of 256 and 130 frames); parameters after one Adam step
+0.0385 and 0.0401.  Every frame's X0 and dC of every pass has the pool's bits, no element is left out as tiny, dC is exactly zero
+off S.  The device lies 10.5 x (N = 2,048) and 47.3 x (1,033) kappa from both dense controls (the last 4 frames lost, counted twice),
+134 and 322 x from a pass of S_blocks with a frame left out, 113 and 130 x from one with a frame read from 1,024 frames earlier.  Held:
+33.07 and 16.93 GiB.  A case takes 2.7 s (N = 2,048, with the float64 pool model; 1.0 s of it on the device passes and comparisons)
+and 0.6 s (N = 1,033).  Broken copies of the library, every access of each inside the workspace, turn both cases red:
+    freqtrain_reduce_kernel stopping one partial early when nblk >= 128     the dense pass's gradients (part b), _proj.weight at 16.4 x
+                                                                            kappa (N = 2,048, 1,856,188 elements) and 11.0 x (1,033)
+    products taking r0 from blk - 1 for blk >= 128                          the dense pass's gradients (part b), _proj.weight at 6.3 x
+                                                                            kappa (N = 2,048, 788,449 elements) and 25.9 x (1,033)
+    the dC tiles reading GatesCat's second direction from the first         the dense pass's dC bits (part b): 264,241,152 elements
+    (dstride taken as 0) from the gate float offset g0 * 512 = 2^25 on,     differ at N = 2,048 (every element from frame 32 on),
+    frame 32 (g0, the pair index, never reaches 2^25: it ends at 2^22)      131,203,072 at N = 1,033
+Unlike the other three trainers, whose dense pass lets the first two pass, this trainer's dbp and dWp sum exact incoming gradients
+and have a kappa of 2e-4 and 9e-4 of the gradient: one lost or repeated row block of 256 or 130 is seen by the dense pass itself."""
 import gc
+import time
 
 import numpy as np
 import pytest
 import torch
 
 import bigbatch_ref64 as BB
+import freqtrain_ref64 as FT
 import headtrain_ref64 as HD
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(v, N) for v, d in BB.VARIANTS.items() for N in d["N"]]
-SLICE = 1024                          # frames of one bit comparison on the device
-MEMORY_CAP = 12 * 2 ** 30
+SLICE = {"freq": 256}                 # frames of one bit comparison on the device: 1,024, and 256 for the frequency LSTM, whose frame's
+                                      # dC is 512 KiB (a slice of the expected dC and its scaled copy are 256 MiB)
+MEMORY_CAP = {("freq", 2048): 34 * 2 ** 30, ("freq", 1033): 18 * 2 ** 30}      # bytes a case may hold on the device: 12 GiB, but for these
 P = BB.POOL
 
 
@@ -124,7 +158,25 @@ class Head:
         return self.tr.backward(dcoef)
 
 
-KINDS = {"lstm": Lstm, "attn": Attn, "head": Head}
+class Freq:
+    fwd_names, bwd_name = ("X0",), "dC"
+
+    def __init__(self, variant):
+        from sdfa_amd.freqtrain import FreqTrainer
+        c = BB.pool_case(variant)                              # 7 frames of 64 columns, shaped as tests/test_gpu_freqtrain.py shapes them
+        self.params = c["params"]
+        self.tr = FreqTrainer(c["params"])
+        self.fin, self.bin = (dev(c["C"].reshape(P, FT.COLS, FT.NS, FT.NI)),), dev(c["dX0"].reshape(P, FT.COLS, FT.NO))
+        self.ref = BB.pool_of(variant)["run"]
+
+    def forward(self, C4):
+        return (self.tr.forward(C4),)
+
+    def backward(self, dX3):
+        return self.tr.backward(dX3, want_dC=True)
+
+
+KINDS = {"lstm": Lstm, "attn": Attn, "head": Head, "freq": Freq}
 
 
 def ratio(what, got, val, kap, worst):
@@ -159,7 +211,7 @@ def scaled(pool, w):
     return pool * w.view((-1,) + (1,) * (pool.dim() - 1))
 
 
-def frames_have_pool_bits(got, pool, jd, wd=None, frames=None):
+def frames_have_pool_bits(got, pool, jd, wd=None, frames=None, SLICE=1024):
     """-> (elements of `got` whose bits are not the pool frame's (times the frame's weight), elements left out as tiny); frames:
     the frames compared (all of them by default).  On the device, SLICE frames at a time."""
     tiny = (pool != 0) & (pool.abs() < BB.TINY) if wd is not None else None
@@ -200,6 +252,8 @@ def largest_batch(variant, N):
     v = BB.VARIANTS[variant]
     ad = KINDS[variant.partition("-")[0]](variant)
     tr, names = ad.tr, ad.fwd_names + (ad.bwd_name,)
+    SL, cap = SLICE.get(variant, 1024), MEMORY_CAP.get((variant, N), 12 * 2 ** 30)
+    t0 = time.perf_counter()
     say = lambda s: print(f"\n{variant} N = {N}: {s}")
 
     # (a) the pool alone against the ref module's float64 run
@@ -222,21 +276,21 @@ def largest_batch(variant, N):
     fin = tuple(t[:P][jd] for t in ad.fin)
     bin_dense = scaled(ad.bin[:P][jd], wd)
     ws_bytes = tr.workspace_bytes(N)
-    slices = 4 * SLICE * pool_bwd[0].numel() * 4               # a slice of the expected dX, its scaled copy, the comparison
+    slices = 4 * SL * pool_bwd[0].numel() * 4                  # a slice of the expected dX, its scaled copy, the comparison
     total = pool_bwd[0].numel() * N
 
     def large_pass(b, what):
         out = ad.forward(*fin) + (ad.backward(b),)
         held = ws_bytes + nbytes(*fin, bin_dense, b if b is not bin_dense else None, *out) + slices
-        assert tr._ws.numel() == ws_bytes and held < MEMORY_CAP, (what, held)
+        assert tr._ws.numel() == ws_bytes and held < cap, (what, held)
         return out, held
 
     # (b) the dense pass
     out, held = large_pass(bin_dense, "dense")
     for n, t, p in zip(names, out, pool_fwd):
-        bad, _ = frames_have_pool_bits(t, p, jd)
+        bad, _ = frames_have_pool_bits(t, p, jd, SLICE=SL)
         assert bad == 0, (n, bad)
-    bad, left_out = frames_have_pool_bits(out[-1], pool_bwd, jd, wd)
+    bad, left_out = frames_have_pool_bits(out[-1], pool_bwd, jd, wd, SLICE=SL)
     assert bad == 0 and left_out <= BB.TINY_SHARE * total, (ad.bwd_name, bad, left_out)
     del out
     g_dense = tr.grads()
@@ -262,9 +316,9 @@ def largest_batch(variant, N):
         dX = out[-1]
         off_S = torch.ones(N, dtype=torch.bool, device=dX.device)
         off_S[Sd] = False
-        not_zero = torch.cat([(dX[s:s + SLICE].reshape(len(dX[s:s + SLICE]), -1) != 0).any(1) for s in range(0, N, SLICE)])
+        not_zero = torch.cat([(dX[s:s + SL].reshape(len(dX[s:s + SL]), -1) != 0).any(1) for s in range(0, N, SL)])
         assert not bool(not_zero[off_S].any()), f"{what}: {ad.bwd_name} is not zero off S"
-        bad, left = frames_have_pool_bits(dX, pool_bwd, jd, wd, Sd)
+        bad, left = frames_have_pool_bits(dX, pool_bwd, jd, wd, Sd, SLICE=SL)
         assert bad == 0 and left <= BB.TINY_SHARE * total, (what, bad, left)
         del out, dX, b
         got = tr.grads()
@@ -299,4 +353,5 @@ def largest_batch(variant, N):
     for n in right["params1"]:
         ratio(f"param:{n}", params[n], right["params1"][n], right["k_params1"][n], worst)
     say(f"the pool's bits again after the large passes; the dense pass's gradient bits again; after one Adam step the largest "
-        f"|gpu - ref64| / kappa on a parameter {worst['param']:.4f}; at most {held / 2 ** 30:.2f} GiB held")
+        f"|gpu - ref64| / kappa on a parameter {worst['param']:.4f}; at most {held / 2 ** 30:.2f} GiB held; the case took "
+        f"{time.perf_counter() - t0:.1f} s")

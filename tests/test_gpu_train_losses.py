@@ -179,6 +179,7 @@ def test_get_loss_on_a_train_batch(synth_sd, head, dynamic):
     model = SaberSpeechDrivenAnimation(hp).load_state_dict(synth_sd[head]).enable_training_objective(synth_sd[head])
     eng, key = model._model._engine, model._model._key
     ts = _train_set(eng.out_dim)
+    torch.cuda.manual_seed(20)                                # the batch's white noise is torch.randn on the device: the same batch in every process
     batch = DSW.train_batch(ts, None, [0, 11, 47], np.random.RandomState(3), hparams=hp)
     z, _ = torch.ops.sdfa.encoder(batch["audio_feat"], key)
     coef = torch.ops.sdfa.regress_coef(z, batch["speaker_id"], key).clone().requires_grad_(True)
