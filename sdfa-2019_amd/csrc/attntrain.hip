@@ -68,7 +68,7 @@ __global__ __launch_bounds__(THREADS) void attntrain_product_kernel(AtProdArgs a
     if (j >= a.B.ni) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t i = i0 + 32 * (wave >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t i = i0 + 32 * (wave >> 1) + tile_row(r, h);
         if (i < a.A.ni) a.out[i * a.ldo + j] = acc[r];
     }
 }
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(THREADS) void attntrain_frame_forward_kernel(AtFwdA
         const float qp = a.qp[n * NA + m], b = a.b[m];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int t = 32 * (wave >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int t = 32 * (wave >> 1) + tile_row(r, h);
             const float u = tanhf(fadd_exact(fadd_exact(acc[ct][r], qp), b));
             un[t * NA + m] = u;
             smem[t * UP + m] = u;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(THREADS) void attntrain_backward_kernel(AtBwdArgs a
         const int o0 = (int)(bid / (QW / T)) * T, j0 = (int)(bid % (QW / T)) * T;
         tile_acc<false, false>(acc, (int)N, Op<0, 0>{a.dqc, 1, D, o0, D, (int)N}, Op<2, 0>{a.H + AT_W0 * D, 1, FRAME, j0, QW, (int)N}, sA, sB);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) a.gWc[(int64_t)(o0 + rr + (r & 3) + 8 * (r >> 2)) * QW + j0 + cj] = acc[r];
+        for (int r = 0; r < 16; ++r) a.gWc[(int64_t)(o0 + rr + tile_row(r, 0)) * QW + j0 + cj] = acc[r];
         return;
     }
     bid -= N_DWC;
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(THREADS) void attntrain_backward_kernel(AtBwdArgs a
         tile_acc<false, false>(acc, C, opA, opB, sA, sB);
         float *out = q ? a.gWq : a.part + blk * NA * D;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) out[(int64_t)(m0 + rr + (r & 3) + 8 * (r >> 2)) * D + c0 + cj] = acc[r];
+        for (int r = 0; r < 16; ++r) out[(int64_t)(m0 + rr + tile_row(r, 0)) * D + c0 + cj] = acc[r];
         return;
     }
     bid -= N_DWQ + (int64_t)a.nblk * N_DWK;
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(THREADS) void attntrain_backward_kernel(AtBwdArgs a
     const float dz = a.dz[n * D + c];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int t = rr + (r & 3) + 8 * (r >> 2);
+        const int t = rr + tile_row(r, 0);
         float v = fmaf(a.al[n * TS + t], dz, acc[r]);
         if (t >= AT_W0 && t < AT_W0 + KW) v = fadd_exact(v, a.dHq[n * QW + (t - AT_W0) * D + c]);
         a.dH[(n * TS + t) * D + c] = v;

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(THREADS) void headtrain_forward_kernel(HtFwdArgs a)
     const float bias = p < jb.P ? jb.bias[p] : 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t n = n0 + 32 * (wave >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t n = n0 + 32 * (wave >> 1) + tile_row(r, h);
         if (n >= N) continue;
         const int64_t s = a.sid[n];
         const bool sok = s >= 0 && s < NS;
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(THREADS) void headtrain_backward_kernel(HtBwdArgs a
         const int k = k0 + 32 * (wave & 1) + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int p = p0 + 32 * (wave >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int p = p0 + 32 * (wave >> 1) + tile_row(r, h);
             if (p >= jb.P) continue;
             if (k < jb.K) dW[(int64_t)p * jb.K + k] = acc[r];
             else if (k == jb.K) db[p] = acc[r];
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(THREADS) void headtrain_backward_kernel(HtBwdArgs a
     const int k = k0 + 32 * (wave & 1) + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t n = n0 + 32 * (wave >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t n = n0 + 32 * (wave >> 1) + tile_row(r, h);
         if (n >= N) continue;
         float v = acc[r];
         if (a.dx_mode != HT_DX_PLAIN) {

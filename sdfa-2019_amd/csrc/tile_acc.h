@@ -81,6 +81,9 @@ __device__ __forceinline__ void tile_acc(f32x16 &acc, const int C, const OA &opA
     }
 }
 
+// the row of accumulator register r inside a wave's 32 x 32 quarter, for the lane half h = lane >> 5
+__device__ __forceinline__ constexpr int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
 __device__ __forceinline__ void zero(f32x16 &acc) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
