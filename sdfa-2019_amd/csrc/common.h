@@ -90,8 +90,9 @@ __device__ __forceinline__ float tanhf_acc(float x) {
 
 // Split of eight floats into NPL bf16 planes, the operand octets of v_mfma_f32_32x32x16_bf16: pl[0] = bf16(x), pl[1] = bf16(x - pl[0]),
 // pl[2] = bf16(x - pl[0] - pl[1]) (both differences are exact in fp32); planes NPL.. are left untouched.  conv.hip and pca.hip split
-// with this.  lstm.hip (split_octet, split_octet3), attn.hip (ks_split8) and gemm.hip (split8) still carry copies of the same arithmetic:
-// their sha1 keys the committed counter records, so they move here with the next counter re-collection.
+// with this.  attn.hip (ks_split8) and gemm.hip (split8) still carry copies of the same arithmetic: their sha1 keys the committed counter
+// records, so they move here with the next counter re-collection.  lstm.hip had that occasion and keeps split_octet / split_octet3: called
+// through this function its bf16 kernels, which sit at 256 VGPRs, compile to other instruction streams (profiles/lstm_stages_ab.txt).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 template <int NPL>
 __device__ __forceinline__ void bf16_split(const float (&x)[8], bf16x8 (&pl)[3]) {

@@ -67,7 +67,7 @@ __device__ __forceinline__ void lstm_cell_quad(const f32x16 &ai, const f32x16 &a
         f32x2 cp = {c[r], c[r + 1]};
         if (FREQ) {
             // Round 4: the accumulators arrive as exponents of two (the host folds log2 e / 2 log2 e into the weights and the bias:
-            // api.cpp), and the cell state is kept in the same units, c~ = 2 log2 e * c (it never leaves the kernel) -- so no gate and
+            // api_model.cpp), and the cell state is kept in the same units, c~ = 2 log2 e * c (it never leaves the kernel) -- so no gate and
             // no tanh(c') argument needs a scaling multiply: 11 packed + 18 transcendental instructions per element pair (16 + 18).
             constexpr float K2 = 2.8853900817779268f;      // 2 log2 e
             const f32x2 ig = rcp2(exp2n(f32x2{ai[r], ai[r + 1]}) + 1.0f);
@@ -94,19 +94,128 @@ __device__ __forceinline__ void lstm_cell_quad(const f32x16 &ai, const f32x16 &a
     hq = make_float4(hv[0].x, hv[0].y, hv[1].x, hv[1].y);
 }
 
+// ------------------------------------------------------------------------------- pieces the kernels below share
+// WEIGHT WINDOW.  Weights are requested through a BUFFER descriptor: wave-uniform base in scalar registers (descriptor inputs made
+// provably uniform with readfirstlane), one loop-invariant 32-bit byte offset per lane, the k-block as scalar offset, the gate as
+// immediate -- no vector-ALU address arithmetic and no 64-bit address registers inside a K loop (with flat addresses the fp32 loops sat
+// at the register limit and the allocator copied half of each refilled operand set at the end of every iteration, behind a full
+// s_waitcnt; the bf16 kernels spilled and their per-step weight prologue was serialised behind scratch reloads).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_rsrc(const void *p, unsigned bytes) {
+    const unsigned long long ptr = (unsigned long long)p;
+    // (readfirstlane returns a SIGNED int: without the casts a low half with bit 31 set sign-extends over the high half)
+    const unsigned long long uni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(ptr >> 32)) << 32) |
+                                   (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ptr);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)uni, 0, (int)bytes, 0x00020000);
+}
+// one 16-byte request: T = float4 or bf16x8; AUX 16 = sc1 (the split kernels' hand-off loads)
+template <typename T, int AUX = 0>
+__device__ __forceinline__ T buf_ld16(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
+    return __builtin_bit_cast(T, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, AUX));
+}
+// the four gate tiles' weight quads of the k-block at scalar offset `so` (gate tiles are 32 rows = 512 bytes apart: immediates)
+__device__ __forceinline__ void wquads(__amdgpu_buffer_rsrc_t rs, unsigned woff, unsigned so, float4 &w0, float4 &w1, float4 &w2, float4 &w3) {
+    w0 = buf_ld16<float4>(rs, woff, so); w1 = buf_ld16<float4>(rs, woff + 512, so);
+    w2 = buf_ld16<float4>(rs, woff + 1024, so); w3 = buf_ld16<float4>(rs, woff + 1536, so);
+}
+
+#define SB() __builtin_amdgcn_sched_barrier(0);
+
+// MFMA GROUP: component q of four weight quads (one per gate tile) against NT operand quads, gate tile outer, column tile inner --
+// consecutive MFMAs go to different accumulators (common.h: mfma_block).  How the group treats C:
+//   SEED_ZERO  (time_lstm_fused_kernel's first group of a step): a literal zero, no zero fill;
+//   SEED_TILE0 (the frequency kernels' first group of a step, NT = 2): column tile 1 starts from tile 0's seeds (C = acc[gt][0],
+//              D = acc[gt][1]) BEFORE tile 0's own first product overwrites them in place -- same sums as seeding both (bitwise).
+enum { SEED_NONE, SEED_ZERO, SEED_TILE0 };
+template <int NT, int SEED = SEED_NONE>
+__device__ __forceinline__ void mfma_group(f32x16 (&acc)[4][NT], const float4 &w0, const float4 &w1, const float4 &w2, const float4 &w3,
+                                           const float4 (&b)[NT], int q) {
+    const float4 *const w[4] = {&w0, &w1, &w2, &w3};
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int gt = 0; gt < 4; ++gt) {
+        if (SEED == SEED_TILE0) {
+            acc[gt][NT - 1] = MFMA(f4c(*w[gt], q), f4c(b[NT - 1], q), acc[gt][0]);
+            acc[gt][0] = MFMA(f4c(*w[gt], q), f4c(b[0], q), acc[gt][0]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[gt][j] = MFMA(f4c(*w[gt], q), f4c(b[j], q), SEED == SEED_ZERO ? zero16 : acc[gt][j]);
+        }
+    }
+}
+
+// K-BLOCK: 16 NT MFMAs on the operand set c* while the set n* is refilled for the next k-block -- its weights at scalar offset `so` of the
+// window (rs, woff), its operand rows at `bp` (per-lane pointer to the row pair).  The six memory instructions of the refill sit one or
+// two at a time in front of the four MFMA groups, pinned with scheduling barriers: each rides in the shadow of the MFMA in flight
+// instead of six in a row outlasting it.  after_w = what rides behind the weight requests, at_b = what rides with
+// the first operand read (time_lstm_fused_kernel's slice staging; nothing elsewhere).
+struct no_hook { __device__ __forceinline__ void operator()() const {} };
+template <int NT, int SEED = SEED_NONE, typename AfterW = no_hook, typename AtB = no_hook>
+__device__ __forceinline__ void k_block(f32x16 (&acc)[4][NT], const float4 &cw0, const float4 &cw1, const float4 &cw2, const float4 &cw3,
+                                        const float4 (&cb)[NT], float4 &nw0, float4 &nw1, float4 &nw2, float4 &nw3, float4 (&nb)[NT],
+                                        __amdgpu_buffer_rsrc_t rs, unsigned woff, unsigned so, const float4 *bp, AfterW after_w = {}, AtB at_b = {}) {
+    SB() nw0 = buf_ld16<float4>(rs, woff, so); nw1 = buf_ld16<float4>(rs, woff + 512, so); SB()
+    mfma_group<NT, SEED>(acc, cw0, cw1, cw2, cw3, cb, 0);
+    SB() nw2 = buf_ld16<float4>(rs, woff + 1024, so); nw3 = buf_ld16<float4>(rs, woff + 1536, so); after_w(); SB()
+    mfma_group<NT>(acc, cw0, cw1, cw2, cw3, cb, 1);
+    SB() at_b(); nb[0] = bp[0]; SB()
+    mfma_group<NT>(acc, cw0, cw1, cw2, cw3, cb, 2);
+    SB() if (NT > 1) nb[NT - 1] = bp[32 * (NT - 1)]; SB()
+    mfma_group<NT>(acc, cw0, cw1, cw2, cw3, cb, 3);
+}
+
+// TRIP: 8 k-blocks with immediate offsets, the two operand sets (wa / ba, wb / bb) in ping-pong; on entry wa / ba hold the trip's k-block 0,
+// on exit the k-block at (son, bn) -- the next trip's first, or behind the last trip k-block 0 again: its operand rows are dropped, its
+// weights ARE k-block 0 of the next step.  KBS = bytes of one k-block of the weight image (1,024 x 16 frequency, 2,048 x 16 time); the
+// operand rows of k-block kb are bt + kb * 2 * BT, BT = 32 NT.  Named scalars for the weights, not arrays: see freq_lstm_v2_kernel.
+// h0 / h3 / h7: time_lstm_fused_kernel's hooks in k-blocks 0, 3 and 7.
+template <int NT, unsigned KBS, int SEED = SEED_NONE, typename H0 = no_hook, typename H3 = no_hook, typename H7 = no_hook>
+__device__ __forceinline__ void k_trip(f32x16 (&acc)[4][NT], float4 &wa0, float4 &wa1, float4 &wa2, float4 &wa3, float4 (&ba)[NT],
+                                       float4 &wb0, float4 &wb1, float4 &wb2, float4 &wb3, float4 (&bb)[NT], __amdgpu_buffer_rsrc_t rs,
+                                       unsigned woff, unsigned so, const float4 *bt, unsigned son, const float4 *bn, H0 h0 = {}, H3 h3 = {}, H7 h7 = {}) {
+    constexpr int BT = 32 * NT;
+    k_block<NT, SEED>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, rs, woff, so + 1 * KBS, bt + 1 * 2 * BT, h0);
+    k_block<NT>(acc, wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, rs, woff, so + 2 * KBS, bt + 2 * 2 * BT);
+    k_block<NT>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, rs, woff, so + 3 * KBS, bt + 3 * 2 * BT);
+    k_block<NT>(acc, wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, rs, woff, so + 4 * KBS, bt + 4 * 2 * BT, no_hook{}, h3);
+    k_block<NT>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, rs, woff, so + 5 * KBS, bt + 5 * 2 * BT);
+    k_block<NT>(acc, wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, rs, woff, so + 6 * KBS, bt + 6 * 2 * BT);
+    k_block<NT>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, rs, woff, so + 7 * KBS, bt + 7 * 2 * BT);
+    k_block<NT>(acc, wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, rs, woff, son, bn, no_hook{}, h7);
+}
+
+// TILE QUEUE of the persistent-capable frequency kernels, at the top of their `for (;;)` over tiles: sets the (direction, 64-column tile)
+// of this pass, or leaves the loop when there is none.
+// PERSIST (option freq_lstm_shape = 5 / 9): a workgroup takes pairs from a queue head in the workspace until the queue is empty; otherwise
+// one hardware-dispatched workgroup per pair, both directions of a column tile on one XCD (block ids 8 apart).
 // SHARED (all frequency-LSTM kernels) = launched over the compacted distinct-column list (column sharing): same code, separate
-// symbol so that profiles keep the two launch shapes apart.
+// symbol so that profiles keep the two launch shapes apart; tiles come in column order, so all behind the first one past the limit are too.
+// (A macro: as a function returning "no tile" the five PERSIST instantiations lose 2 - 16 scalar instructions of this prologue, and a
+// kernel here is held to the parent's instruction count: profiles/lstm_stages_ab.txt.)
+#define NEXT_TILE(a, sTile, n_tiles, dir, m0)                                                                 \
+    if (PERSIST) {                                                                                               \
+        if (tid == 0) *(sTile) = atomicAdd(a.tile_counter, 1);                                                   \
+        __syncthreads();                       /* (also: every wave has left the previous tile's last step) */   \
+        const int t = __builtin_amdgcn_readfirstlane(*(sTile));                                                  \
+        if (t >= n_tiles) break;               /* queue empty: every workgroup gets here */                      \
+        dir = t & 1;                                                                                             \
+        m0 = (int64_t)(t >> 1) * 64;                                                                             \
+        if (SHARED && m0 >= *a.col_limit) break;                                                                 \
+    } else {                                                                                                     \
+        dir = (blockIdx.x >> 3) & 1;                                                                             \
+        m0 = (int64_t)(((blockIdx.x >> 4) << 3) | (blockIdx.x & 7)) * 64;                                        \
+        if (SHARED && m0 >= *a.col_limit) return;                                                                \
+    }
 
 // ------------------------------------------------------------------------------- frequency LSTM, second form
-// Same arithmetic and the same per-accumulator order of operations as freq_lstm_kernel<.., 2, 2> (bit-identical output);
-// what changed is WHEN things are requested and in which order the MFMAs are issued:
+// Same arithmetic and the same per-accumulator order of operations as the first form (the round-1 freq_lstm_kernel, removed in
+// round 3; bit-identical output); what changed is WHEN things are requested and in which order the MFMAs are issued:
 //   * the next x_f tile goes HBM -> LDS directly (global_load_lds_dwordx4 into the idle half of sX: no registers, no
 //     staging stores), requested right after the K loop instead of at the top of the step.  Loads return in issue order,
 //     so a tile requested before the first weight quads made every step's first MFMA wait for an HBM round trip;
 //   * k-block 0 of the weights is requested for the NEXT step right after the K loop and stays live across the cell update
-//     (the 16 registers the x tile no longer needs); all weight requests go through a buffer descriptor (scalar base +
-//     per-lane 32-bit offset: no vector-ALU address arithmetic, no 64-bit address registers);
-//   * MFMAs are issued component-major (mfma_block): consecutive MFMAs go to different accumulators, so a wave that
+//     (the 16 registers the x tile no longer needs); all weight requests go through the weight window (wave_rsrc);
+//   * MFMAs are issued component-major (mfma_group): consecutive MFMAs go to different accumulators, so a wave that
 //     has the matrix pipe to itself -- its partner workgroup is in its cell update -- does not stall on the previous
 //     MFMA's result every time;
 //   * the barrier after the K loop is a bare s_barrier (every LDS read has been consumed by an MFMA by then): it does
@@ -136,19 +245,7 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
   for (;;) {      // PERSIST: one pass per tile taken from the queue; otherwise a single pass
     int dir;
     int64_t m0;
-    if (PERSIST) {
-        if (tid == 0) sTile = atomicAdd(a.tile_counter, 1);
-        __syncthreads();                       // (also: every wave has left the previous tile's last step)
-        const int t = __builtin_amdgcn_readfirstlane(sTile);
-        if (t >= n_tiles) break;               // queue empty: every workgroup gets here
-        dir = t & 1;
-        m0 = (int64_t)(t >> 1) * BT;
-        if (SHARED && m0 >= *a.col_limit) break;      // tiles come in column order: all later ones are past the limit too
-    } else {
-        dir = (blockIdx.x >> 3) & 1;
-        m0 = (int64_t)(((blockIdx.x >> 4) << 3) | (blockIdx.x & 7)) * BT;
-        if (SHARED && m0 >= *a.col_limit) return;
-    }
+    NEXT_TILE(a, &sTile, n_tiles, dir, m0)
     const float4 *__restrict__ W = reinterpret_cast<const float4 *>(a.W) + (size_t)dir * 48 * 512;
 
     sBias[tid] = a.bias[dir * 512 + tid];
@@ -156,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
 
     // x_f tile = 16 k-quad rows of 64 columns (1 KiB each): wave w moves rows w, w+4, w+8, w+12
     const float4 *__restrict__ xsrc = X3 + (int64_t)wave * a.Mc + m0 + lane;
-#define XDMA(f, buf)                                                                                                   \
+#define XDMA(f, buf)                                                                                                  \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                      \
         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(xsrc + (int64_t)((f)*16 + 4 * i) * a.Mc), \
                                          (void __attribute__((address_space(3))) *)(&sX[buf][4 * i + wave][0]), 16, 0, 0);
@@ -168,41 +265,16 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) c[j][r] = 0.f;
 
-    // weight quads through a BUFFER descriptor: wave-uniform base in scalar registers (descriptor inputs made provably
-    // uniform with readfirstlane), one loop-invariant 32-bit byte offset per lane, the k-block as scalar offset, the gate as
-    // immediate -- no vector-ALU address arithmetic and no 64-bit address registers inside the K loop (with flat addresses
-    // the loop sat at the register limit and the allocator copied half of each refilled operand set at the end of every
-    // iteration, behind a full s_waitcnt)
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const unsigned long long wptr = (unsigned long long)(W + wave * 128);
-    // (readfirstlane returns a SIGNED int: without the casts a low half with bit 31 set sign-extends over the high half)
-    const unsigned long long wuni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wptr >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wptr);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wuni, 0, 48 * 512 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(W + wave * 128, 48 * 512 * 16);
     const unsigned woff = (unsigned)((l31 + h * 512) * 16);
-#define FV_W1(so, g_) __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + 512 * (g_), so, 0))
-#define FV_WLOAD(kb, W0, W1, W2, W3)                                                                         \
-    {                                                                                                        \
-        const unsigned so = (unsigned)(kb) * (1024 * 16);                                                    \
-        W0 = FV_W1(so, 0); W1 = FV_W1(so, 1); W2 = FV_W1(so, 2); W3 = FV_W1(so, 3);                          \
-    }
-#define FV_BLOAD(kb, B0, B1)                                                                                 \
+#define FV_WLOAD(kb, W0, W1, W2, W3) wquads(wrs, woff, (unsigned)(kb) * (1024 * 16), W0, W1, W2, W3);
+#define FV_BLOAD(kb, B)                                                                                      \
     {                                                                                                        \
         const float4 *bsrc = (kb) < 8 ? &sX[cur][2 * (kb) + h][0] : &sH[2 * ((kb) - 8) + h][0];              \
-        B0 = bsrc[l31]; B1 = bsrc[32 + l31];                                                                 \
+        B[0] = bsrc[l31]; B[1] = bsrc[32 + l31];                                                             \
     }
     // one k-block: 32 MFMAs, component-major (consecutive MFMAs go to different accumulators)
-#define FV_MFMA(W0, W1, W2, W3, B0, B1)                                                                      \
-    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                          \
-        acc[0][0] = MFMA(f4c(W0, q), f4c(B0, q), acc[0][0]);                                                 \
-        acc[0][1] = MFMA(f4c(W0, q), f4c(B1, q), acc[0][1]);                                                 \
-        acc[1][0] = MFMA(f4c(W1, q), f4c(B0, q), acc[1][0]);                                                 \
-        acc[1][1] = MFMA(f4c(W1, q), f4c(B1, q), acc[1][1]);                                                 \
-        acc[2][0] = MFMA(f4c(W2, q), f4c(B0, q), acc[2][0]);                                                 \
-        acc[2][1] = MFMA(f4c(W2, q), f4c(B1, q), acc[2][1]);                                                 \
-        acc[3][0] = MFMA(f4c(W3, q), f4c(B0, q), acc[3][0]);                                                 \
-        acc[3][1] = MFMA(f4c(W3, q), f4c(B1, q), acc[3][1]);                                                 \
-    }
+#define FV_MFMA(W0, W1, W2, W3, B) _Pragma("unroll") for (int q = 0; q < 4; ++q) mfma_group<NJ>(acc, W0, W1, W2, W3, B, q);
     float4 wn0, wn1, wn2, wn3;
     FV_WLOAD(0, wn0, wn1, wn2, wn3)
     __syncthreads();   // bias and the first x tile are in LDS (the fence drains the DMA)
@@ -212,10 +284,10 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
         const int cur = s & 1;
         // Two alternating operand sets (wa/ba, wb/bb), each refilled right after the MFMAs that read it were issued: requests
         // run one k-block (32 MFMAs) ahead.  k-block 0 comes from `wn`, requested during the previous step's cell update.
-        // Named scalars, not arrays: with arrays (or with one set that is loop-carried through BOTH loops, or with the K loop
-        // unrolled completely) the register allocator loaded refills into scratch registers and copied them over behind a
-        // full s_waitcnt at the end of every K iteration, or spilled 253 registers.
-        float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba0, ba1, bb0, bb1;
+        // Named scalars for the weights, not arrays: with arrays (or with one set that is loop-carried through BOTH loops, or with
+        // the K loop unrolled completely) the register allocator loaded refills into scratch registers and copied them over behind
+        // a full s_waitcnt at the end of every K iteration, or spilled 253 registers.
+        float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba[NJ], bb[NJ];
         f32x16 acc[4][NJ];
 #pragma unroll
         for (int gt = 0; gt < 4; ++gt)
@@ -229,21 +301,21 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
                 }
             }
         const int nkb = s > 0 ? 24 : 8;        // h_{-1} = 0: the first step contracts x_f only
-        FV_BLOAD(0, ba0, ba1)
+        FV_BLOAD(0, ba)
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll 1
         for (int kb = 0; kb < nkb; kb += 2) {
             FV_WLOAD(kb + 1, wb0, wb1, wb2, wb3)
-            FV_BLOAD(kb + 1, bb0, bb1)
-            __builtin_amdgcn_sched_barrier(0);
-            FV_MFMA(wa0, wa1, wa2, wa3, ba0, ba1)
-            __builtin_amdgcn_sched_barrier(0);
+            FV_BLOAD(kb + 1, bb)
+            SB()
+            FV_MFMA(wa0, wa1, wa2, wa3, ba)
+            SB()
             const int kb2 = kb + 2 < nkb ? kb + 2 : 0;   // branch-free: the last iteration re-requests k-block 0 and drops it
             FV_WLOAD(kb2, wa0, wa1, wa2, wa3)
-            FV_BLOAD(kb2, ba0, ba1)
-            __builtin_amdgcn_sched_barrier(0);
-            FV_MFMA(wb0, wb1, wb2, wb3, bb0, bb1)
-            __builtin_amdgcn_sched_barrier(0);
+            FV_BLOAD(kb2, ba)
+            SB()
+            FV_MFMA(wb0, wb1, wb2, wb3, bb)
+            SB()
         }
         FV_WLOAD(0, wn0, wn1, wn2, wn3)     // k-block 0 for the NEXT step: in flight during the cell update (weights do not change)
         __builtin_amdgcn_s_setprio(0);
@@ -278,7 +350,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v2_kernel(FreqLstmArgs a) {
 #undef FV_WLOAD
 #undef FV_BLOAD
 #undef FV_MFMA
-#undef FV_W1
 }
 
 // ------------------------------------------------------------------------------- frequency LSTM, third form
@@ -309,23 +380,10 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
     const float4 *__restrict__ X3 = reinterpret_cast<const float4 *>(a.X3);
     float4 *__restrict__ HF = reinterpret_cast<float4 *>(a.HF);
     const int n_tiles = (int)(a.Mc / BT) * 2;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   for (;;) {      // PERSIST: one pass per tile taken from the queue; otherwise a single pass
     int dir;
     int64_t m0;
-    if (PERSIST) {
-        if (tid == 0) *sTile = atomicAdd(a.tile_counter, 1);
-        __syncthreads();                       // (also: every wave has left the previous tile's last step)
-        const int t = __builtin_amdgcn_readfirstlane(*sTile);
-        if (t >= n_tiles) break;               // queue empty: every workgroup gets here
-        dir = t & 1;
-        m0 = (int64_t)(t >> 1) * BT;
-        if (SHARED && m0 >= *a.col_limit) break;
-    } else {
-        dir = (blockIdx.x >> 3) & 1;
-        m0 = (int64_t)(((blockIdx.x >> 4) << 3) | (blockIdx.x & 7)) * BT;
-        if (SHARED && m0 >= *a.col_limit) return;
-    }
+    NEXT_TILE(a, sTile, n_tiles, dir, m0)
     const float4 *__restrict__ W = reinterpret_cast<const float4 *>(a.W) + (size_t)dir * 48 * 512;
     sBias[tid] = a.bias[dir * 512 + tid];
     sBias[256 + tid] = a.bias[dir * 512 + 256 + tid];
@@ -344,86 +402,10 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) c[j][r] = 0.f;
 
-    // weight quads through a buffer descriptor, as in the second form
-    const unsigned long long wptr = (unsigned long long)(W + wave * 128);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wptr, 0, 48 * 512 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(W + wave * 128, 48 * 512 * 16);
     const unsigned woff = (unsigned)((l31 + h * 512) * 16);
-#define F3_W(so, g_) __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + 512 * (g_), so, 0))
-#define F3_SB() __builtin_amdgcn_sched_barrier(0);
-#define F3_Q(W0, W1, W2, W3, B0, B1, q)                                                                      \
-    {                                                                                                        \
-        acc[0][0] = MFMA(f4c(W0, q), f4c(B0, q), acc[0][0]);                                                 \
-        acc[0][1] = MFMA(f4c(W0, q), f4c(B1, q), acc[0][1]);                                                 \
-        acc[1][0] = MFMA(f4c(W1, q), f4c(B0, q), acc[1][0]);                                                 \
-        acc[1][1] = MFMA(f4c(W1, q), f4c(B1, q), acc[1][1]);                                                 \
-        acc[2][0] = MFMA(f4c(W2, q), f4c(B0, q), acc[2][0]);                                                 \
-        acc[2][1] = MFMA(f4c(W2, q), f4c(B1, q), acc[2][1]);                                                 \
-        acc[3][0] = MFMA(f4c(W3, q), f4c(B0, q), acc[3][0]);                                                 \
-        acc[3][1] = MFMA(f4c(W3, q), f4c(B1, q), acc[3][1]);                                                 \
-    }
-    // the step's very first MFMA group: column tile 1 starts from tile 0's seeds (C = acc[gt][0], D = acc[gt][1]) BEFORE tile 0's own
-    // first product overwrites them in place -- same sums as seeding both (bitwise)
-#define F3_QSEED(W0, W1, W2, W3, B0, B1)                                                                     \
-    {                                                                                                        \
-        acc[0][1] = MFMA(f4c(W0, 0), f4c(B1, 0), acc[0][0]);                                                 \
-        acc[0][0] = MFMA(f4c(W0, 0), f4c(B0, 0), acc[0][0]);                                                 \
-        acc[1][1] = MFMA(f4c(W1, 0), f4c(B1, 0), acc[1][0]);                                                 \
-        acc[1][0] = MFMA(f4c(W1, 0), f4c(B0, 0), acc[1][0]);                                                 \
-        acc[2][1] = MFMA(f4c(W2, 0), f4c(B1, 0), acc[2][0]);                                                 \
-        acc[2][0] = MFMA(f4c(W2, 0), f4c(B0, 0), acc[2][0]);                                                 \
-        acc[3][1] = MFMA(f4c(W3, 0), f4c(B1, 0), acc[3][0]);                                                 \
-        acc[3][0] = MFMA(f4c(W3, 0), f4c(B0, 0), acc[3][0]);                                                 \
-    }
-    // one k-block on the operand set C* while the set N* is refilled for the next one: weights at scalar offset `so`,
-    // operand rows at `bp` (per-lane pointer to the row pair of the next k-block).  F3_KB_SEED: the step's first k-block
-#define F3_KB_SEED(CW0, CW1, CW2, CW3, CB0, CB1, NW0, NW1, NW2, NW3, NB0, NB1, so, bp)                       \
-    {                                                                                                        \
-        F3_SB() NW0 = F3_W(so, 0); NW1 = F3_W(so, 1); F3_SB()                                                \
-        F3_QSEED(CW0, CW1, CW2, CW3, CB0, CB1)                                                               \
-        F3_SB() NW2 = F3_W(so, 2); NW3 = F3_W(so, 3); F3_SB()                                                \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 1)                                                                \
-        F3_SB() NB0 = (bp)[0]; F3_SB()                                                                       \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 2)                                                                \
-        F3_SB() NB1 = (bp)[32]; F3_SB()                                                                      \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 3)                                                                \
-    }
-#define F3_KB(CW0, CW1, CW2, CW3, CB0, CB1, NW0, NW1, NW2, NW3, NB0, NB1, so, bp)                            \
-    {                                                                                                        \
-        F3_SB() NW0 = F3_W(so, 0); NW1 = F3_W(so, 1); F3_SB()                                                \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 0)                                                                \
-        F3_SB() NW2 = F3_W(so, 2); NW3 = F3_W(so, 3); F3_SB()                                                \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 1)                                                                \
-        F3_SB() NB0 = (bp)[0]; F3_SB()                                                                       \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 2)                                                                \
-        F3_SB() NB1 = (bp)[32]; F3_SB()                                                                      \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 3)                                                                \
-    }
-    // the last k-block of a step: the same, with the four LDS-DMA requests of the next x tile behind its last two MFMA
-    // groups -- an LDS-DMA request takes ~100 cycles to issue (profiles/HISTORY.md), four in a row in front of the cell update
-    // cost 400; here most of that rides in the MFMAs' shadow.  They come AFTER this k-block's weight requests, so the next
-    // step's first weight wait (loads return in issue order) does not include the tile's HBM round trip.
-#define F3_KB_LAST(CW0, CW1, CW2, CW3, CB0, CB1, NW0, NW1, NW2, NW3, NB0, NB1, so, bp, dma, fnext, par)      \
-    {                                                                                                        \
-        F3_SB() NW0 = F3_W(so, 0); NW1 = F3_W(so, 1); F3_SB()                                                \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 0)                                                                \
-        F3_SB() NW2 = F3_W(so, 2); NW3 = F3_W(so, 3); F3_SB()                                                \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 1)                                                                \
-        F3_SB() NB0 = (bp)[0]; NB1 = (bp)[32];      /* both LDS reads BEFORE the first DMA request: the compiler puts a full  \
-                                                       vmcnt(0) in front of any LDS read that follows one */ \
-        if (dma) { XDMA3_HALF(fnext, par, 0) }                                                               \
-        F3_SB()                                                                                              \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 2)                                                                \
-        F3_SB()                                                                                              \
-        if (dma) { XDMA3_HALF(fnext, par, 2) }                                                               \
-        F3_SB()                                                                                              \
-        F3_Q(CW0, CW1, CW2, CW3, CB0, CB1, 3)                                                                \
-    }
-#define XDMA3_HALF(f, par, i0)                                                                                         \
-    _Pragma("unroll") for (int i = (i0); i < (i0) + 2; ++i)                                                            \
-        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(xsrc + (int64_t)((f)*16 + 4 * i) * a.Mc), \
-                                         (void __attribute__((address_space(3))) *)(&sXH[par][4 * i + wave][0]), 16, 0, 0);
-    float4 wa0, wa1, wa2, wa3, wb0, wb1, wb2, wb3, ba0, ba1, bb0, bb1;
-    wa0 = F3_W(0u, 0); wa1 = F3_W(0u, 1); wa2 = F3_W(0u, 2); wa3 = F3_W(0u, 3);
+    float4 wa0, wa1, wa2, wa3, wb0, wb1, wb2, wb3, ba[NJ], bb[NJ];
+    wquads(wrs, woff, 0u, wa0, wa1, wa2, wa3);
     __syncthreads();   // bias and the first x tile are in LDS (the fence drains the DMA)
 
     for (int s = 0; s < 32; ++s) {
@@ -433,14 +415,14 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
         // the first k-block's operand rows FIRST (LDS answers a wave's reads in order): the step's first MFMA then waits for these two and
         // its own four seed quads, the later seeds land under the MFMAs in front of them
         const float4 *brow = &sXH[cur][h][l31];                 // row pair of k-block kb: brow + kb * 2 * BT
-        ba0 = brow[0]; ba1 = brow[32];
-        F3_SB()
+        ba[0] = brow[0]; ba[1] = brow[32];
+        SB()
 #pragma unroll
         for (int gt = 0; gt < 4; ++gt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 // Seeds (the bias) go into column tile 0's accumulators ONLY; tile 1's first MFMA of the step takes them from there as its C
-                // operand (F3_QSEED below) -- D != C costs nothing.  History: one read + a v_mov per register of the second tile cost 64
+                // operand (SEED_TILE0 below) -- D != C costs nothing.  History: one read + a v_mov per register of the second tile cost 64
                 // vector instructions per step (0.6 ms of the 114.5); a second read per quad removed those but left 32 reads of 1 KiB
                 // per wave in front of every step's first MFMA, and the CU's LDS moves 4 waves x 34 KiB in ~550 cycles.
                 const float4 b = *reinterpret_cast<const float4 *>(&sBias[wave * 128 + gt * 32 + 8 * g + 4 * h]);
@@ -450,26 +432,17 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
         const int trips = s > 0 ? 3 : 1;       // h_{-1} = 0: the first step contracts x_f only (8 of the 24 k-blocks)
         // a trip = 8 k-blocks.  Trip 0 is written out in front of the loop: its first MFMA group is the seeded one, and as straight-line code
         // the compiler sees that (a run-time `t == 0` inside the loop made it copy the 128 accumulator registers of tile 1 around the branch)
-#define F3_TRIP(FIRST_KB, t_)                                                                                                     \
-        {                                                                                                                         \
-            const float4 *bt = brow + (t_) * 16 * BT;                                                                             \
-            const float4 *bn = (t_) + 1 < trips ? bt + 16 * BT : brow;      /* behind the last trip: k-block 0 again (dropped) */  \
-            const unsigned so = (unsigned)(t_) * (8 * 1024 * 16);                                                                 \
-            const unsigned son = (t_) + 1 < trips ? so + 8 * 1024 * 16 : 0u; /* ... whose weights ARE k-block 0 of the next step */ \
-            FIRST_KB(wa0, wa1, wa2, wa3, ba0, ba1, wb0, wb1, wb2, wb3, bb0, bb1, so + 1 * 1024 * 16, bt + 1 * 2 * BT)             \
-            F3_KB(wb0, wb1, wb2, wb3, bb0, bb1, wa0, wa1, wa2, wa3, ba0, ba1, so + 2 * 1024 * 16, bt + 2 * 2 * BT)                \
-            F3_KB(wa0, wa1, wa2, wa3, ba0, ba1, wb0, wb1, wb2, wb3, bb0, bb1, so + 3 * 1024 * 16, bt + 3 * 2 * BT)                \
-            F3_KB(wb0, wb1, wb2, wb3, bb0, bb1, wa0, wa1, wa2, wa3, ba0, ba1, so + 4 * 1024 * 16, bt + 4 * 2 * BT)                \
-            F3_KB(wa0, wa1, wa2, wa3, ba0, ba1, wb0, wb1, wb2, wb3, bb0, bb1, so + 5 * 1024 * 16, bt + 5 * 2 * BT)                \
-            F3_KB(wb0, wb1, wb2, wb3, bb0, bb1, wa0, wa1, wa2, wa3, ba0, ba1, so + 6 * 1024 * 16, bt + 6 * 2 * BT)                \
-            F3_KB(wa0, wa1, wa2, wa3, ba0, ba1, wb0, wb1, wb2, wb3, bb0, bb1, so + 7 * 1024 * 16, bt + 7 * 2 * BT)                \
-            F3_KB(wb0, wb1, wb2, wb3, bb0, bb1, wa0, wa1, wa2, wa3, ba0, ba1, son, bn)                                            \
-        }
-        F3_TRIP(F3_KB_SEED, 0)
+        constexpr unsigned KBS = 1024 * 16, TRIP = 8 * KBS;
+        const float4 *const bn0 = trips > 1 ? brow + 16 * BT : brow;
+        k_trip<NJ, KBS, SEED_TILE0>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, wrs, woff, 0u, brow, trips > 1 ? TRIP : 0u, bn0);
 #pragma unroll 1
-        for (int t = 1; t < trips; ++t) F3_TRIP(F3_KB, t)
-#undef F3_TRIP
-        F3_SB()
+        for (int t = 1; t < trips; ++t) {
+            const float4 *bt = brow + t * 16 * BT;
+            const unsigned so = (unsigned)t * TRIP;
+            k_trip<NJ, KBS>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, wrs, woff, so, bt, t + 1 < trips ? so + TRIP : 0u,
+                            t + 1 < trips ? bt + 16 * BT : brow);
+        }
+        SB()
         // The next x tile: four plain 16-byte loads per lane into registers, requested here -- BEHIND the step's last weight
         // requests, so that no weight wait includes their HBM round trip (loads return in issue order) -- and written to the
         // OTHER parity's buffer after the cell update, which covers the round trip.  (An LDS-DMA request for these rows, 8 MB
@@ -497,14 +470,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
 #undef XDMA3
-#undef XDMA3_HALF
-#undef F3_KB_LAST
-#undef F3_KB_SEED
-#undef F3_QSEED
-#undef F3_W
-#undef F3_SB
-#undef F3_Q
-#undef F3_KB
     if (!PERSIST) break;
   }
 }
@@ -518,10 +483,12 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_v3_kernel(FreqLstmArgs a) {
 // row/column, lane half = which 8 of the 16 k).  x_f is split while it is staged (octet o = K4 quads 2o, 2o+1);
 // h is split by the lane that produced it, which owns rows 32w+8g+4h+{0..3} for g = 0..3 -- so octet 4w+2q+h holds
 // hidden units 32w+16q+4h+{0..3} and 32w+16q+8+4h+{0..3}, and the host packs W_hh's K axis in that same order
-// (api.cpp: pack_freq_lstm_bf16).  Weights arrive pre-split (hi plane, lo plane) and stream from L2 as before.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+// (api_model.cpp: pack_freq_lstm_bf16).  Weights arrive pre-split (hi plane, lo plane) and stream from L2 as before.
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
+// (The arithmetic of bf16_split<2> / <3> in common.h, kept as its own text: through bf16_split time_lstm_bf16_kernel<2, 3> spills one
+// register more and freq_lstm_bf16x6_kernel, freq_lstm_bf16p_v3_kernel<.., 3> and time_lstm_bf16_kernel<1, 6> change their streams --
+// profiles/lstm_stages_ab.txt.)
 __device__ __forceinline__ void split_octet(const float4 &x0, const float4 &x1, bf16x8 &hi, bf16x8 &lo) {
     const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
@@ -531,8 +498,6 @@ __device__ __forceinline__ void split_octet(const float4 &x0, const float4 &x1, 
         lo[e] = (__bf16)(x[e] - (float)hb);
     }
 }
-
-// x = hi + mid + lo, three bf16 terms (24 significand bits): the six-product split (SDFA_PREC_BF16X6)
 __device__ __forceinline__ void split_octet3(const float4 &x0, const float4 &x1, bf16x8 &hi, bf16x8 &mid, bf16x8 &lo) {
     const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
@@ -573,15 +538,10 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16x6_kernel(FreqLstmArgs a
     if (SHARED && m0 >= *a.col_limit) return;
 
     const float4 *__restrict__ X3 = reinterpret_cast<const float4 *>(a.X3);
-    // weights through a buffer descriptor: uniform base + ONE 32-bit lane offset + a scalar offset per (plane, k-step) -- no 64-bit
-    // address registers (with lane pointers the kernel spilled and its per-step weight prologue was serialised behind scratch reloads)
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const unsigned long long wptr6 = (unsigned long long)(reinterpret_cast<const bf16x8 *>(a.Wb) + (size_t)dir * BF16_PLANES * 24 * 512);
-    const unsigned long long wuni6 = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wptr6 >> 32)) << 32) |
-                                     (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wptr6);
-    const __amdgpu_buffer_rsrc_t wrs6 = __builtin_amdgcn_make_buffer_rsrc((void *)wuni6, 0, BF16_PLANES * 24 * 512 * 16, 0x00020000);
+    // the weight window: uniform base + ONE 32-bit lane offset + a scalar offset per (plane, k-step)
+    const __amdgpu_buffer_rsrc_t wrs6 = wave_rsrc(reinterpret_cast<const bf16x8 *>(a.Wb) + (size_t)dir * BF16_PLANES * 24 * 512, BF16_PLANES * 24 * 512 * 16);
     const unsigned woff6 = (unsigned)((wave * 128 + l31 + h * 512) * 16);
-#define F6_W(pl, ks, gt) __builtin_bit_cast(bf16x8, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs6, woff6 + (unsigned)(gt) * 512u, (unsigned)(((pl) * 24 + 2 * (ks)) * 512 * 16), 0))
+#define F6_W(pl, ks, gt) buf_ld16<bf16x8>(wrs6, woff6 + (unsigned)(gt) * 512u, (unsigned)(((pl) * 24 + 2 * (ks)) * 512 * 16))
     float4 *__restrict__ HF = reinterpret_cast<float4 *>(a.HF);
 
     sBias[tid] = a.bias[dir * 512 + tid];
@@ -741,7 +701,6 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16p_v3_kernel(FreqLstmArgs
     const float4 *__restrict__ X3 = reinterpret_cast<const float4 *>(a.X3);
     float4 *__restrict__ HF = reinterpret_cast<float4 *>(a.HF);
     const int n_tiles = (int)(a.Mc / BT) * 2;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     const unsigned woff = (unsigned)((wave * 128 + l31 + h * 512) * 16);
     constexpr unsigned W_PLANE = 24u * 512u * 16u, W_KS = 2u * 512u * 16u;      // bytes: one plane, one k-step (two octet rows of 512 gate rows)
 #define P6_SB() __builtin_amdgcn_sched_barrier(0);
@@ -798,21 +757,8 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16p_v3_kernel(FreqLstmArgs
   for (;;) {      // PERSIST: one pass per tile taken from the queue; otherwise a single pass
     int dir;
     int64_t m0;
-    if (PERSIST) {
-        if (tid == 0) *sTile = atomicAdd(a.tile_counter, 1);
-        __syncthreads();                       // (also: every wave has left the previous tile's last step)
-        const int t = __builtin_amdgcn_readfirstlane(*sTile);
-        if (t >= n_tiles) break;               // queue empty: every workgroup gets here
-        dir = t & 1;
-        m0 = (int64_t)(t >> 1) * BT;
-        if (SHARED && m0 >= *a.col_limit) break;
-    } else {
-        dir = (blockIdx.x >> 3) & 1;
-        m0 = (int64_t)(((blockIdx.x >> 4) << 3) | (blockIdx.x & 7)) * BT;
-        if (SHARED && m0 >= *a.col_limit) return;
-    }
-    const unsigned long long wptr = (unsigned long long)(reinterpret_cast<const bf16x8 *>(a.Wb) + (size_t)dir * BF16_PLANES * 24 * 512);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wptr, 0, BF16_PLANES * 24 * 512 * 16, 0x00020000);
+    NEXT_TILE(a, sTile, n_tiles, dir, m0)
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(reinterpret_cast<const bf16x8 *>(a.Wb) + (size_t)dir * BF16_PLANES * 24 * 512, BF16_PLANES * 24 * 512 * 16);
     sBias[tid] = a.bias[dir * 512 + tid];
     sBias[256 + tid] = a.bias[dir * 512 + 256 + tid];
 
@@ -1067,12 +1013,25 @@ __global__ __launch_bounds__(256, 2) void freq_lstm_bf16_kernel(FreqLstmArgs a) 
 }
 
 // ----------------------------------------------------------------------------------------- time LSTM
+// Quad g of column tile j in the cell update of the eight-wave time kernels: h_t to the other parity's LDS rows (sHn: the next step's
+// operand) and to the H output rows (Hl: this lane's row pair and columns; tcol = t * Nc).  The quad's gate registers are free afterwards.
+template <int NT>
+__device__ __forceinline__ void time_cell_quad(f32x16 (&acc)[4][NT], f32x16 &c, int g, int j, float4 *sHn, float4 *__restrict__ Hl, int64_t Mc,
+                                               int64_t tcol, int wave, int h, int l31) {
+    float4 hq;
+    lstm_cell_quad(acc[0][j], acc[1][j], acc[2][j], acc[3][j], c, g, hq);
+    const int hq_idx = 8 * wave + 2 * g + h;
+    sHn[hq_idx * (32 * NT) + j * 32 + l31] = hq;
+    Hl[(int64_t)(2 * g) * Mc + tcol + j * 32] = hq;
+}
+
 // NT = 32-frame column tiles per workgroup: 2 (64 frames, the throughput shape) or 1 (32 frames: twice the
 // workgroups, used when a chunk would otherwise leave CUs idle).
 // MAP (column sharing, layer 0): GX holds the input projection of the DISTINCT columns only (a.col_map[t * Nc + n] = its column), so a
 // lane's 32 quads of a step come from column u = col_map[...] instead of t * Nc + n.  Within a clip the frames of a tile map to one
 // run of consecutive u (they all shift by the same 12 frames / 25 hops), so the requests stay coalesced; u is fetched one step
 // further ahead than the quads it addresses, behind that step's requests, and costs no wait of its own.
+
 template <int NT, bool MAP = false>
 __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
     extern __shared__ float4 sHt[];   // [2][64 k-quads][32*NT sequences]
@@ -1119,20 +1078,14 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
             }
 
     // Recurrent weights one k-block ahead, two alternating operand sets, branch-free (see freq_lstm_v2_kernel): named
-    // scalars and a buffer descriptor (wave-uniform base in scalar registers + one 32-bit lane offset), so the K loop
-    // carries no copies and no 64-bit address registers.  The request that wraps around at the end of a step's K loop IS
-    // k-block 0 of the next step (weights do not change): it goes into `wn`, which stays live across the cell update and
-    // the step barrier, so the first MFMAs after the barrier (all 8 waves start together) do not wait for L2.
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const unsigned long long wptr = (unsigned long long)(reinterpret_cast<const float4 *>(a.W) + (size_t)dir * 64 * 1024 + wave * 128);
-    const unsigned long long wuni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wptr >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wptr);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wuni, 0, 64 * 1024 * 16, 0x00020000);
+    // scalars and the weight window, so the K loop carries no copies and no 64-bit address registers.  The request that
+    // wraps around at the end of a step's K loop IS k-block 0 of the next step (weights do not change): it goes into `wn`,
+    // which stays live across the cell update and the step barrier, so the first MFMAs after the barrier (all 8 waves start
+    // together) do not wait for L2.
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(reinterpret_cast<const float4 *>(a.W) + (size_t)dir * 64 * 1024 + wave * 128, 64 * 1024 * 16);
     const unsigned woff = (unsigned)((l31 + h * 1024) * 16);
-#define TL_W1(so, g_) __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + 512 * (g_), so, 0))
-#define TL_LOAD(kb, W0, W1, W2, W3) { const unsigned so = (unsigned)(kb) * (2048 * 16); W0 = TL_W1(so, 0); W1 = TL_W1(so, 1); W2 = TL_W1(so, 2); W3 = TL_W1(so, 3); }
     float4 wn0, wn1, wn2, wn3;
-    TL_LOAD(0, wn0, wn1, wn2, wn3)
+    wquads(wrs, woff, 0u, wn0, wn1, wn2, wn3);
     if (MAP) {      // columns of step 1's request (behind step 0's quads, in front of the first weights)
 #pragma unroll
         for (int j = 0; j < NT; ++j) ucol[j] = cmap[(int64_t)(dir ? 62 : 1) * a.Nc + j * 32];
@@ -1146,58 +1099,26 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
 
         if (s > 0) {
             float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba[NT], bb[NT];
-            // K loop in trips of 8 k-blocks with immediate offsets, the memory instructions that refill the other operand set
-            // one or two at a time in front of the four MFMA groups of a k-block (freq_lstm_v3_kernel)
-#define TL_SB() __builtin_amdgcn_sched_barrier(0);
-#define TL_Q(W0, W1, W2, W3, B, q)                                                                               \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[0][j] = MFMA(f4c(W0, q), f4c(B[j], q), acc[0][j]);        \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[1][j] = MFMA(f4c(W1, q), f4c(B[j], q), acc[1][j]);        \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[2][j] = MFMA(f4c(W2, q), f4c(B[j], q), acc[2][j]);        \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[3][j] = MFMA(f4c(W3, q), f4c(B[j], q), acc[3][j]);
-#define TL_KB(CW0, CW1, CW2, CW3, CB, NW0, NW1, NW2, NW3, NB, so, bp)                                            \
-    {                                                                                                            \
-        TL_SB() NW0 = TL_W1(so, 0); NW1 = TL_W1(so, 1); TL_SB()                                                  \
-        TL_Q(CW0, CW1, CW2, CW3, CB, 0)                                                                          \
-        TL_SB() NW2 = TL_W1(so, 2); NW3 = TL_W1(so, 3); TL_SB()                                                  \
-        TL_Q(CW0, CW1, CW2, CW3, CB, 1)                                                                          \
-        TL_SB() NB[0] = (bp)[0]; TL_SB()                                                                         \
-        TL_Q(CW0, CW1, CW2, CW3, CB, 2)                                                                          \
-        TL_SB() if (NT > 1) NB[NT - 1] = (bp)[32 * (NT - 1)]; TL_SB()                                            \
-        TL_Q(CW0, CW1, CW2, CW3, CB, 3)                                                                          \
-    }
+            // K loop in trips of 8 k-blocks (k_trip)
+            constexpr unsigned KBS = 2048 * 16, TRIP = 8 * KBS;
             const float4 *brow = sHc + h * BT + l31;          // row pair of k-block kb: brow + kb * 2 * BT
 #pragma unroll
             for (int j = 0; j < NT; ++j) ba[j] = brow[j * 32];
 #pragma unroll 1
             for (int t = 0; t < 4; ++t) {
                 const float4 *bt = brow + t * 16 * BT;
-                const float4 *bn = t + 1 < 4 ? bt + 16 * BT : brow;         // behind the last trip: k-block 0 again (dropped) ...
-                const unsigned so = (unsigned)t * (8 * 2048 * 16);
-                const unsigned son = t + 1 < 4 ? so + 8 * 2048 * 16 : 0u;   // ... whose weights ARE k-block 0 of the next step
-                TL_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 1 * 2048 * 16, bt + 1 * 2 * BT)
-                TL_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 2 * 2048 * 16, bt + 2 * 2 * BT)
-                TL_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 3 * 2048 * 16, bt + 3 * 2 * BT)
-                TL_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 4 * 2048 * 16, bt + 4 * 2 * BT)
-                TL_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 5 * 2048 * 16, bt + 5 * 2 * BT)
-                TL_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 6 * 2048 * 16, bt + 6 * 2 * BT)
-                TL_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 7 * 2048 * 16, bt + 7 * 2 * BT)
-                TL_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, son, bn)
+                const unsigned so = (unsigned)t * TRIP;
+                k_trip<NT, KBS>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, wrs, woff, so, bt, t + 1 < 4 ? so + TRIP : 0u,
+                                t + 1 < 4 ? bt + 16 * BT : brow);
             }
-            TL_SB()
-#undef TL_KB
-#undef TL_Q
-#undef TL_SB
+            SB()
             wn0 = wa0; wn1 = wa1; wn2 = wa2; wn3 = wa3;      // k-block 0 again: the next step's first operands
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                float4 hq;
-                lstm_cell_quad(acc[0][j], acc[1][j], acc[2][j], acc[3][j], c[j], g, hq);
-                const int hq_idx = 8 * wave + 2 * g + h;
-                sHn[hq_idx * BT + j * 32 + l31] = hq;
-                Hl[(int64_t)(2 * g) * a.Mc + tcol + j * 32] = hq;
+                time_cell_quad<NT>(acc, c[j], g, j, sHn, Hl, a.Mc, tcol, wave, h, l31);
                 if (s + 1 < 64) {   // this quad's gate registers are free: request the next step's input projection into them
 #pragma unroll
                     for (int gt = 0; gt < 4; ++gt) {
@@ -1214,8 +1135,6 @@ __device__ __forceinline__ void time_lstm_body(const TimeLstmArgs &a) {
         __syncthreads();   // h_s complete in sHn before anyone reads it; sHc free for step s+1's writes
     }
 #undef TL_GX
-#undef TL_LOAD
-#undef TL_W1
 }
 
 template <int NT, bool MAP = false>
@@ -1273,69 +1192,31 @@ __global__ __launch_bounds__(512, 2) void time_lstm_fused_kernel(TimeLstmArgs a)
 
     // weights: one image per direction, [128 k-quads of W_ih | 64 of W_hh][1024 gate rows][4], through a buffer descriptor one
     // k-block ahead (see time_lstm_body); the request that wraps around at the end of a step is k-block 0 of the next step
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const unsigned long long wptr = (unsigned long long)(reinterpret_cast<const float4 *>(a.Wxh) + (size_t)dir * 192 * 1024 + wave * 128);
-    const unsigned long long wuni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wptr >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wptr);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wuni, 0, (192 * 1024 - 7 * 128) * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(reinterpret_cast<const float4 *>(a.Wxh) + (size_t)dir * 192 * 1024 + wave * 128, (192 * 1024 - 7 * 128) * 16);
     const unsigned woff = (unsigned)((l31 + h * 1024) * 16);
-#define TF_W1(so, g_) __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + 512 * (g_), so, 0))
-    constexpr unsigned KB = 2048 * 16;      // bytes of one k-block of the image
+    constexpr unsigned KBS = 2048 * 16, TRIP = 8 * KBS;      // bytes of one k-block of the image, of one trip
     float4 wn0, wn1, wn2, wn3;
     TF_XLOAD(dir ? 63 : 0, 0)
-    wn0 = TF_W1(0u, 0); wn1 = TF_W1(0u, 1); wn2 = TF_W1(0u, 2); wn3 = TF_W1(0u, 3);
+    wquads(wrs, woff, 0u, wn0, wn1, wn2, wn3);
     TF_XSTORE(0)
     __syncthreads();
 
-#define TF_SB() __builtin_amdgcn_sched_barrier(0);
-#define TF_Q(W0, W1, W2, W3, B, q)                                                                               \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[0][j] = MFMA(f4c(W0, q), f4c(B[j], q), acc[0][j]);        \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[1][j] = MFMA(f4c(W1, q), f4c(B[j], q), acc[1][j]);        \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[2][j] = MFMA(f4c(W2, q), f4c(B[j], q), acc[2][j]);        \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[3][j] = MFMA(f4c(W3, q), f4c(B[j], q), acc[3][j]);
-    // the step's first MFMA group: C = 0
-#define TF_QZ(W0, W1, W2, W3, B, q)                                                                              \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[0][j] = MFMA(f4c(W0, q), f4c(B[j], q), zero16);           \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[1][j] = MFMA(f4c(W1, q), f4c(B[j], q), zero16);           \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[2][j] = MFMA(f4c(W2, q), f4c(B[j], q), zero16);           \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[3][j] = MFMA(f4c(W3, q), f4c(B[j], q), zero16);
-    // one k-block on the operand set C* while the set N* is refilled for the next one (time_lstm_body's TL_KB); Q0 = its first
-    // MFMA group, AFTER_W = what rides behind its weight requests, AT_B = what rides with its first operand read
-#define TF_KB_(Q0, AFTER_W, AT_B, CW0, CW1, CW2, CW3, CB, NW0, NW1, NW2, NW3, NB, so, bp)                        \
-    {                                                                                                            \
-        TF_SB() NW0 = TF_W1(so, 0); NW1 = TF_W1(so, 1); TF_SB()                                                  \
-        Q0(CW0, CW1, CW2, CW3, CB, 0)                                                                            \
-        TF_SB() NW2 = TF_W1(so, 2); NW3 = TF_W1(so, 3); AFTER_W TF_SB()                                          \
-        TF_Q(CW0, CW1, CW2, CW3, CB, 1)                                                                          \
-        TF_SB() AT_B NB[0] = (bp)[0]; TF_SB()                                                                    \
-        TF_Q(CW0, CW1, CW2, CW3, CB, 2)                                                                          \
-        TF_SB() if (NT > 1) NB[NT - 1] = (bp)[32 * (NT - 1)]; TF_SB()                                            \
-        TF_Q(CW0, CW1, CW2, CW3, CB, 3)                                                                          \
-    }
-#define TF_NONE
-#define TF_KB(...) TF_KB_(TF_Q, TF_NONE, TF_NONE, __VA_ARGS__)
-    // every wave's slice writes (and its reads of the buffer they replace, one trip back) are done: hand the buffer over
-#define TF_HANDOVER asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // a trip of the x part: 8 k-blocks on x buffer (i & 1); the next slice is requested in k-block 0, written in k-block 3 and handed
-    // over in k-block 7, in front of the first read of it (the operands of the next trip's k-block 0)
-#define TF_XTRIP(Q0, i_)                                                                                                          \
+    // a trip of the x part: 8 k-blocks on x buffer (i & 1); the next slice is requested behind the weight requests of k-block 0, written
+    // with the first operand read of k-block 3 and handed over in k-block 7 (every wave's slice writes, and its reads of the buffer they
+    // replace, one trip back, are done), in front of the first read of it (the operands of the next trip's k-block 0)
+#define TF_XTRIP(SEED, i_)                                                                                                        \
     {                                                                                                                             \
         const int nb = ((i_) & 1) ^ 1;                                                                                            \
         const float4 *bt = xrow + ((i_) & 1) * 16 * BT;                                                                           \
         const float4 *bn = (i_) < 7 ? xrow + nb * 16 * BT : hrow;                                                                 \
-        const unsigned so = (unsigned)(i_) * (8 * KB);                                                                            \
-        const unsigned son = ((i_) < 7 || s > 0) ? so + 8 * KB : 0u;     /* step 0 has no h part: k-block 0 of the next step */   \
+        const unsigned so = (unsigned)(i_) * TRIP;                                                                                \
+        const unsigned son = ((i_) < 7 || s > 0) ? so + TRIP : 0u;       /* step 0 has no h part: k-block 0 of the next step */   \
         const int tl = (i_) < 7 ? t : tn, sl = (i_) < 7 ? (i_) + 1 : 0;                                                           \
-        TF_KB_(Q0, TF_XLOAD(tl, sl), TF_NONE, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 1 * KB, bt + 1 * 2 * BT)      \
-        TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 2 * KB, bt + 2 * 2 * BT)                                       \
-        TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 3 * KB, bt + 3 * 2 * BT)                                       \
-        TF_KB_(TF_Q, TF_NONE, TF_XSTORE(nb), wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 4 * KB, bt + 4 * 2 * BT)        \
-        TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 5 * KB, bt + 5 * 2 * BT)                                       \
-        TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 6 * KB, bt + 6 * 2 * BT)                                       \
-        TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 7 * KB, bt + 7 * 2 * BT)                                       \
-        TF_KB_(TF_Q, TF_NONE, TF_HANDOVER, wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, son, bn)                               \
+        k_trip<NT, KBS, SEED>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, wrs, woff, so, bt, son, bn,                    \
+                              [&]() __attribute__((always_inline)) { TF_XLOAD(tl, sl) },                                          \
+                              [&]() __attribute__((always_inline)) { TF_XSTORE(nb) },                                             \
+                              [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }); \
     }
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const float4 *const xrow = sX + h * BT + l31;         // row pair of k-block kb of an x trip: xrow + buffer * 16 * BT + kb * 2 * BT
     for (int s = 0; s < 64; ++s) {
         const int t = dir ? 63 - s : s;
@@ -1350,49 +1231,27 @@ __global__ __launch_bounds__(512, 2) void time_lstm_fused_kernel(TimeLstmArgs a)
         for (int j = 0; j < NT; ++j) ba[j] = xrow[j * 32];
         // trip 0 is written out in front of the loop: its first MFMA group is the zero-seeded one (a run-time test inside the loop
         // would make the compiler copy accumulators around the branch: freq_lstm_v3_kernel)
-        TF_XTRIP(TF_QZ, 0)
+        TF_XTRIP(SEED_ZERO, 0)
 #pragma unroll 1
-        for (int i = 1; i < 8; ++i) TF_XTRIP(TF_Q, i)
+        for (int i = 1; i < 8; ++i) TF_XTRIP(SEED_NONE, i)
         if (s > 0) {      // h_{-1} = 0: the first step contracts x only
 #pragma unroll 1
             for (int tr = 0; tr < 4; ++tr) {
                 const float4 *bt = hrow + tr * 16 * BT;
-                const float4 *bn = tr + 1 < 4 ? bt + 16 * BT : xrow;        // behind the last trip: dropped ...
-                const unsigned so = (unsigned)(8 + tr) * (8 * KB);
-                const unsigned son = tr + 1 < 4 ? so + 8 * KB : 0u;         // ... whose weights ARE k-block 0 of the next step
-                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 1 * KB, bt + 1 * 2 * BT)
-                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 2 * KB, bt + 2 * 2 * BT)
-                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 3 * KB, bt + 3 * 2 * BT)
-                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 4 * KB, bt + 4 * 2 * BT)
-                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 5 * KB, bt + 5 * 2 * BT)
-                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 6 * KB, bt + 6 * 2 * BT)
-                TF_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 7 * KB, bt + 7 * 2 * BT)
-                TF_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, son, bn)
+                const unsigned so = (unsigned)(8 + tr) * TRIP;
+                k_trip<NT, KBS>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, wrs, woff, so, bt, tr + 1 < 4 ? so + TRIP : 0u,
+                                tr + 1 < 4 ? bt + 16 * BT : xrow);      // behind the last trip: operand rows that are dropped
             }
         }
-        TF_SB()
+        SB()
         wn0 = wa0; wn1 = wa1; wn2 = wa2; wn3 = wa3;      // k-block 0 again: the next step's first operands
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float4 hq;
-                lstm_cell_quad(acc[0][j], acc[1][j], acc[2][j], acc[3][j], c[j], g, hq);
-                const int hq_idx = 8 * wave + 2 * g + h;
-                sHn[hq_idx * BT + j * 32 + l31] = hq;
-                Hl[(int64_t)(2 * g) * a.Mc + tcol + j * 32] = hq;
-            }
+            for (int g = 0; g < 4; ++g) time_cell_quad<NT>(acc, c[j], g, j, sHn, Hl, a.Mc, tcol, wave, h, l31);
         __syncthreads();   // h_s complete in sHn before anyone reads it; the other parity free for step s+1's writes
     }
 #undef TF_XTRIP
-#undef TF_HANDOVER
-#undef TF_KB
-#undef TF_NONE
-#undef TF_KB_
-#undef TF_QZ
-#undef TF_Q
-#undef TF_SB
-#undef TF_W1
 #undef TF_XSTORE
 #undef TF_XLOAD
 }
@@ -1470,7 +1329,6 @@ __global__ __launch_bounds__(512 / G) void time_lstm_split_kernel(TimeLstmArgs a
     const int mode = ctl.mode;
     extern __shared__ float4 sHs[];   // [2][64 k-quads][32 sequences]
     constexpr int BT = 32, NW = 8 / G, NTHR = 64 * NW;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
@@ -1498,20 +1356,13 @@ __global__ __launch_bounds__(512 / G) void time_lstm_split_kernel(TimeLstmArgs a
     if (MAP) ucol = cmap[(int64_t)(dir ? 62 : 1) * a.Nc];
 
     // H rows of this direction as a buffer: write-through stores of the own slice, sc1 loads of the partners' slices
-    const unsigned long long hptr = (unsigned long long)(reinterpret_cast<float4 *>(a.H) + (int64_t)dir * 64 * a.Mc);
-    const unsigned long long huni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(hptr >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)hptr);
-    const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc((void *)huni, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t hrs = wave_rsrc(reinterpret_cast<float4 *>(a.H) + (int64_t)dir * 64 * a.Mc, 0x7fffffff);
     const unsigned ldm = (unsigned)a.Mc * 16u;                           // bytes per k-quad row (launcher: 64 rows stay below 2 GB)
 
-    const unsigned long long wptr = (unsigned long long)(reinterpret_cast<const float4 *>(a.W) + (size_t)dir * 64 * 1024 + hb * 128);
-    const unsigned long long wuni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wptr >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wptr);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wuni, 0, 64 * 1024 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(reinterpret_cast<const float4 *>(a.W) + (size_t)dir * 64 * 1024 + hb * 128, 64 * 1024 * 16);
     const unsigned woff = (unsigned)((l31 + h * 1024) * 16);
-#define TS_W1(so, g_) __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + 512 * (g_), so, 0))
     float4 wn0, wn1, wn2, wn3;
-    { wn0 = TS_W1(0u, 0); wn1 = TS_W1(0u, 1); wn2 = TS_W1(0u, 2); wn3 = TS_W1(0u, 3); }
+    wquads(wrs, woff, 0u, wn0, wn1, wn2, wn3);
     unsigned *my_flag = flags + (size_t)td * G + part;
     bool dead = false;                 // a poll timed out: stop waiting for partners (the result is wrong and the timeout word says so)
     for (int s = 0; s < 64; ++s) {
@@ -1522,44 +1373,18 @@ __global__ __launch_bounds__(512 / G) void time_lstm_split_kernel(TimeLstmArgs a
         float4 *sHn = sHs + (size_t)((s & 1) ^ 1) * 64 * BT;
 
         if (s > 0) {
-            float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba, bb;
-#define TS_SB() __builtin_amdgcn_sched_barrier(0);
-#define TS_Q(W0, W1, W2, W3, B, q)                                              \
-    acc[0][0] = MFMA(f4c(W0, q), f4c(B, q), acc[0][0]);                         \
-    acc[1][0] = MFMA(f4c(W1, q), f4c(B, q), acc[1][0]);                         \
-    acc[2][0] = MFMA(f4c(W2, q), f4c(B, q), acc[2][0]);                         \
-    acc[3][0] = MFMA(f4c(W3, q), f4c(B, q), acc[3][0]);
-#define TS_KB(CW0, CW1, CW2, CW3, CB, NW0, NW1, NW2, NW3, NB, so, bp)           \
-    {                                                                           \
-        TS_SB() NW0 = TS_W1(so, 0); NW1 = TS_W1(so, 1); TS_SB()                 \
-        TS_Q(CW0, CW1, CW2, CW3, CB, 0)                                         \
-        TS_SB() NW2 = TS_W1(so, 2); NW3 = TS_W1(so, 3); TS_SB()                 \
-        TS_Q(CW0, CW1, CW2, CW3, CB, 1)                                         \
-        TS_SB() NB = (bp)[0]; TS_SB()                                           \
-        TS_Q(CW0, CW1, CW2, CW3, CB, 2)                                         \
-        TS_Q(CW0, CW1, CW2, CW3, CB, 3)                                         \
-    }
+            float4 wa0 = wn0, wa1 = wn1, wa2 = wn2, wa3 = wn3, wb0, wb1, wb2, wb3, ba[1], bb[1];
+            constexpr unsigned KBS = 2048 * 16, TRIP = 8 * KBS;
             const float4 *brow = sHc + h * BT + l31;          // row pair of k-block kb: brow + kb * 2 * BT
-            ba = brow[0];
+            ba[0] = brow[0];
 #pragma unroll 1
             for (int tt = 0; tt < 4; ++tt) {
                 const float4 *bt = brow + tt * 16 * BT;
-                const float4 *bn = tt + 1 < 4 ? bt + 16 * BT : brow;
-                const unsigned so = (unsigned)tt * (8 * 2048 * 16);
-                const unsigned son = tt + 1 < 4 ? so + 8 * 2048 * 16 : 0u;
-                TS_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 1 * 2048 * 16, bt + 1 * 2 * BT)
-                TS_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 2 * 2048 * 16, bt + 2 * 2 * BT)
-                TS_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 3 * 2048 * 16, bt + 3 * 2 * BT)
-                TS_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 4 * 2048 * 16, bt + 4 * 2 * BT)
-                TS_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 5 * 2048 * 16, bt + 5 * 2 * BT)
-                TS_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, so + 6 * 2048 * 16, bt + 6 * 2 * BT)
-                TS_KB(wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, so + 7 * 2048 * 16, bt + 7 * 2 * BT)
-                TS_KB(wb0, wb1, wb2, wb3, bb, wa0, wa1, wa2, wa3, ba, son, bn)
+                const unsigned so = (unsigned)tt * TRIP;
+                k_trip<1, KBS>(acc, wa0, wa1, wa2, wa3, ba, wb0, wb1, wb2, wb3, bb, wrs, woff, so, bt, tt + 1 < 4 ? so + TRIP : 0u,
+                               tt + 1 < 4 ? bt + 16 * BT : brow);
             }
-            TS_SB()
-#undef TS_KB
-#undef TS_Q
-#undef TS_SB
+            SB()
             wn0 = wa0; wn1 = wa1; wn2 = wa2; wn3 = wa3;
         }
         // cell update: own slice of h_t -> LDS (next step's operand) and -> the H output rows, write-through
@@ -1612,8 +1437,8 @@ __global__ __launch_bounds__(512 / G) void time_lstm_split_kernel(TimeLstmArgs a
             for (int i = 0; i < PER; ++i) {
                 const int idx = i * NTHR + tid, r = idx >> 5, col = idx & 31;
                 const int kq = r < part * (64 / G) ? r : r + 64 / G;      // skip the own slice
-                if (mode & 2) pv[i] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(hrs, (unsigned)kq * ldm + (unsigned)col * 16u, tcol, 0));
-                else pv[i] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(hrs, (unsigned)kq * ldm + (unsigned)col * 16u, tcol, 16));
+                if (mode & 2) pv[i] = buf_ld16<float4>(hrs, (unsigned)kq * ldm + (unsigned)col * 16u, tcol);
+                else pv[i] = buf_ld16<float4, 16>(hrs, (unsigned)kq * ldm + (unsigned)col * 16u, tcol);
             }
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
@@ -1626,7 +1451,6 @@ __global__ __launch_bounds__(512 / G) void time_lstm_split_kernel(TimeLstmArgs a
     }
 #undef TS_GX
 #undef TS_GX_ALL
-#undef TS_W1
 }
 
 // ------------------------------------------------------------------- time LSTM, small batches, 16-frame tiles
@@ -1639,7 +1463,7 @@ __global__ __launch_bounds__(512 / G) void time_lstm_split_kernel(TimeLstmArgs a
 // only on the ORDER in which a gate row's 256 products are added.  The 32x32x2 kernels add, per k-block kb, the pairs (8kb+q, 8kb+4+q),
 // q = 0..3 (K4 operands: lane half 0 holds k-quad 2kb, half 1 k-quad 2kb+1).  Here one MFMA adds FOUR products, lane group g = l >> 4
 // supplying the g-th: MFMA (kb, m), m = 0, 1, takes k = 8kb + {0, 4, 1, 5} (m = 0) / {2, 6, 3, 7} (m = 1) -- the same sequence.  Both
-// operands are stored in that order: the weights by the host ([K16 = kb / 2][g][gate row][j = 2 (kb & 1) + m], api.cpp), h by the lanes
+// operands are stored in that order: the weights by the host ([K16 = kb / 2][g][gate row][j = 2 (kb & 1) + m], api_model.cpp), h by the lanes
 // that produce it (LDS [K16][g][frame][j]), so one 16-byte read per lane feeds four consecutive MFMAs.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -1667,7 +1491,6 @@ __global__ __launch_bounds__(256) void time_lstm_split16_kernel(TimeLstmArgs a, 
     unsigned *const flags = ctl.flags;
     const int mode = ctl.mode;
     extern __shared__ float4 sH16[];   // [2 buffers][16 K16][4 g][16 frames] float4 (j = 0..3): 2 x 16 KiB
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f = lane & 15, lg = lane >> 4;
     const int q8 = blockIdx.x >> 3;
@@ -1691,19 +1514,13 @@ __global__ __launch_bounds__(256) void time_lstm_split16_kernel(TimeLstmArgs a, 
     T16_GX_ALL(dir ? 63 : 0)
     if (MAP) ucol = cmap[(int64_t)(dir ? 62 : 1) * a.Nc];
 
-    const unsigned long long hptr = (unsigned long long)(reinterpret_cast<float4 *>(a.H) + (int64_t)dir * 64 * a.Mc);
-    const unsigned long long huni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(hptr >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)hptr);
-    const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc((void *)huni, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t hrs = wave_rsrc(reinterpret_cast<float4 *>(a.H) + (int64_t)dir * 64 * a.Mc, 0x7fffffff);
     const unsigned ldm = (unsigned)a.Mc * 16u;
 
     // weights of this direction: float4 [16 K16][4 g][1024 rows]; lane (row-in-tile f, group lg) reads [K16][lg][hb*128 + tile*16 + f]
-    const unsigned long long wptr = (unsigned long long)(reinterpret_cast<const float4 *>(a.W16) + (size_t)dir * 16 * 4 * 1024 + hb * 128);
-    const unsigned long long wuni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wptr >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wptr);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)wuni, 0, 16 * 4 * 1024 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(reinterpret_cast<const float4 *>(a.W16) + (size_t)dir * 16 * 4 * 1024 + hb * 128, 16 * 4 * 1024 * 16);
     const unsigned woff = (unsigned)((lg * 1024 + f) * 16);
-#define T16_W(K16, tile) __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + (unsigned)(tile) * 256u, (unsigned)(K16) * (4 * 1024 * 16), 0))
+#define T16_W(K16, tile) buf_ld16<float4>(wrs, woff + (unsigned)(tile) * 256u, (unsigned)(K16) * (4 * 1024 * 16))
 
     unsigned *my_flag = flags + (size_t)td * 2 + part;
     const unsigned *partner_flag = flags + (size_t)td * 2 + (part ^ 1);
@@ -1779,8 +1596,8 @@ __global__ __launch_bounds__(256) void time_lstm_split16_kernel(TimeLstmArgs a, 
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int idx = i * 256 + tid, q = (part ^ 1) * 32 + (idx >> 4), col = idx & 15;
-                if (mode & 2) pv[i] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(hrs, (unsigned)q * ldm + (unsigned)col * 16u + tcol, 0, 0));
-                else pv[i] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(hrs, (unsigned)q * ldm + (unsigned)col * 16u + tcol, 0, 16));
+                if (mode & 2) pv[i] = buf_ld16<float4>(hrs, (unsigned)q * ldm + (unsigned)col * 16u + tcol, 0);
+                else pv[i] = buf_ld16<float4, 16>(hrs, (unsigned)q * ldm + (unsigned)col * 16u + tcol, 0);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -1803,7 +1620,7 @@ __global__ __launch_bounds__(256) void time_lstm_split16_kernel(TimeLstmArgs a, 
 // Mixed-precision modes: the BiLSTM recurrence h_{t-1} * W_hh^T on v_mfma_f32_32x32x16_bf16 (TERMS 1 or 3, see
 // freq_lstm_bf16_kernel); input projection (from the GEMM), accumulation, cell state and gate math stay fp32.
 // h lives in LDS as bf16x8 octets, split by the lane that produced it: octet 4w + 2q + h holds hidden units
-// 32w+16q+4h+{0..3} and 32w+16q+8+4h+{0..3}; the host packs W_hh's K axis in that order (api.cpp: pack_rec_bf16).
+// 32w+16q+4h+{0..3} and 32w+16q+8+4h+{0..3}; the host packs W_hh's K axis in that order (api_model.cpp: pack_rec_bf16).
 template <int NT, int TERMS>
 __global__ __launch_bounds__(512, 2) void time_lstm_bf16_kernel(TimeLstmArgs a) {
     constexpr bool LO = TERMS > 1, X6 = TERMS == 6;      // X6: the six-product split (see freq_lstm_bf16x6_kernel), NT = 1 only (96 KiB of LDS)
@@ -1848,11 +1665,9 @@ __global__ __launch_bounds__(512, 2) void time_lstm_bf16_kernel(TimeLstmArgs a) 
 
     // the recurrent weights through a buffer descriptor (one per direction: [plane][32 octet rows][1024 gate rows] of 16 bytes): a request is
     // descriptor + uniform byte offset (plane, k-step) + one loop-invariant lane offset -- no 64-bit address arithmetic in the K loop
-    typedef unsigned int tb_u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16x8 *>(reinterpret_cast<const bf16x8 *>(a.Wb) + (size_t)dir * BF16_PLANES * 32 * 1024), 0, BF16_PLANES * 32 * 1024 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = wave_rsrc(reinterpret_cast<const bf16x8 *>(a.Wb) + (size_t)dir * BF16_PLANES * 32 * 1024, BF16_PLANES * 32 * 1024 * 16);
     const unsigned woff = (unsigned)((h * 1024 + wave * 128 + l31) * 16);
-#define TB_W(pl, ks_, gt) __builtin_bit_cast(bf16x8, (tb_u32x4)__builtin_amdgcn_raw_buffer_load_b128(wrs, woff + (unsigned)(gt) * 512u, (unsigned)(((pl) * 32 + 2 * (ks_)) * 1024 * 16), 0))
+#define TB_W(pl, ks_, gt) buf_ld16<bf16x8>(wrs, woff + (unsigned)(gt) * 512u, (unsigned)(((pl) * 32 + 2 * (ks_)) * 1024 * 16))
     bf16x8 R[4], S[4], H6a[4], H6b[4];        // three-product form: R = hi, S = lo plane; six-product form: H6a / H6b = hi (ping-pong), R = mid, S = lo
     if (!X6) {
 #pragma unroll
@@ -2005,7 +1820,22 @@ __global__ __launch_bounds__(512, 2) void time_lstm_bf16_kernel(TimeLstmArgs a) 
 #undef TB_W
 }
 
+#undef NEXT_TILE
+#undef SB
+
 }  // namespace
+
+// Every launch of this file: raise the kernel's dynamic-LDS limit where it asks for any (per launch: cheap, and correct for every
+// device / thread the library is used from), launch, return the launch's status.
+template <typename... P, typename... A>
+static hipError_t launch_lds(void (*kernel)(P...), unsigned grid, unsigned block, size_t lds, hipStream_t s, const A &...args) {
+    if (lds) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, s, args...);
+    return hipGetLastError();
+}
 
 // Launch forms of the fp32 recurrence (FreqLstmArgs::shape; all bit-identical):
 //   9  freq_lstm_v3_kernel, persistent (tile queue), one workgroup per CU   -- default
@@ -2018,74 +1848,40 @@ template <bool SHARED>
 static hipError_t launch_freq(const FreqLstmArgs &a, hipStream_t s) {
     const int shape = (a.shape == 8 || a.shape == 5 || a.shape == 3) ? a.shape : 9;
     const unsigned n_tiles = (unsigned)(a.Mc / 64 * 2);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    cus = std::max(1, cus - a.reserve_cus);      // CUs left to kernels of other streams (sdfa_model_set_reserved_cus)
-    if (shape == 8 || shape == 9) {      // the third form: one workgroup per CU by construction (96 KiB of LDS)
-        const size_t lds = 2 * 48 * 64 * sizeof(float4) + 512 * sizeof(float) + 16;
-        const void *fn = shape == 9 ? reinterpret_cast<const void *>(freq_lstm_v3_kernel<SHARED, true>) : reinterpret_cast<const void *>(freq_lstm_v3_kernel<SHARED, false>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (shape == 9) {
-            e = hipMemsetAsync(a.tile_counter, 0, sizeof(int), s);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((freq_lstm_v3_kernel<SHARED, true>), dim3(n_tiles < (unsigned)cus ? n_tiles : (unsigned)cus), dim3(256), lds, s, a);
-        } else {
-            hipLaunchKernelGGL((freq_lstm_v3_kernel<SHARED, false>), dim3(n_tiles), dim3(256), lds, s, a);
-        }
-        return hipGetLastError();
-    }
-    if (shape == 5) {                    // persistent: workgroups pull tiles from a queue, two per CU
-        const unsigned slots = 2u * (unsigned)cus;
-        hipError_t e = hipMemsetAsync(a.tile_counter, 0, sizeof(int), s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((freq_lstm_v2_kernel<SHARED, true>), dim3(n_tiles < slots ? n_tiles : slots), dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((freq_lstm_v2_kernel<SHARED, false>), dim3(n_tiles), dim3(256), 0, s, a);
-    return hipGetLastError();
+    const unsigned cus = (unsigned)std::max(1, sdfa_cu_count() - a.reserve_cus);      // CUs left to kernels of other streams (sdfa_model_set_reserved_cus)
+    const size_t lds3 = 2 * 48 * 64 * sizeof(float4) + 512 * sizeof(float) + 16;       // the third form: one workgroup per CU by construction (96 KiB of LDS)
+    if (shape == 8) return launch_lds(freq_lstm_v3_kernel<SHARED, false>, n_tiles, 256, lds3, s, a);
+    if (shape == 3) return launch_lds(freq_lstm_v2_kernel<SHARED, false>, n_tiles, 256, 0, s, a);
+    // persistent: workgroups pull tiles from a queue, one (third form) or two (second form) per CU
+    const hipError_t e = hipMemsetAsync(a.tile_counter, 0, sizeof(int), s);
+    if (e != hipSuccess) return e;
+    if (shape == 9) return launch_lds(freq_lstm_v3_kernel<SHARED, true>, std::min(n_tiles, cus), 256, lds3, s, a);
+    return launch_lds(freq_lstm_v2_kernel<SHARED, true>, std::min(n_tiles, 2u * cus), 256, 0, s, a);
 }
 
 template <bool SHARED>
 static hipError_t launch_freq_bf16(const FreqLstmArgs &a, hipStream_t s) {
     if (!a.Wb) return hipErrorInvalidValue;
+    const unsigned n_tiles = (unsigned)(a.Mc / 64 * 2);
     if ((a.terms == 6 || a.terms == 3) && a.shape != 3) {      // default: one persistent workgroup per CU (shape 8: one hardware-dispatched workgroup per tile)
         const int pl = a.terms == 6 ? 3 : 2;
         const size_t lds = (size_t)(2 * pl * 24 * 64) * sizeof(bf16x8) + 512 * sizeof(float) + 16;         // 146 KiB / 98 KiB
-        const unsigned n_tiles = (unsigned)(a.Mc / 64 * 2);
         const bool persist = a.shape != 8;
-        const void *fn = pl == 3 ? (persist ? reinterpret_cast<const void *>(freq_lstm_bf16p_v3_kernel<SHARED, true, 3>) : reinterpret_cast<const void *>(freq_lstm_bf16p_v3_kernel<SHARED, false, 3>))
-                                 : (persist ? reinterpret_cast<const void *>(freq_lstm_bf16p_v3_kernel<SHARED, true, 2>) : reinterpret_cast<const void *>(freq_lstm_bf16p_v3_kernel<SHARED, false, 2>));
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+        void (*const kernel)(FreqLstmArgs) = pl == 3 ? (persist ? freq_lstm_bf16p_v3_kernel<SHARED, true, 3> : freq_lstm_bf16p_v3_kernel<SHARED, false, 3>)
+                                                     : (persist ? freq_lstm_bf16p_v3_kernel<SHARED, true, 2> : freq_lstm_bf16p_v3_kernel<SHARED, false, 2>);
         unsigned grid = n_tiles;
         if (persist) {
-            const unsigned cus = (unsigned)std::max(1, sdfa_cu_count() - a.reserve_cus);
-            grid = n_tiles < cus ? n_tiles : cus;
-            e = hipMemsetAsync(a.tile_counter, 0, sizeof(int), s);
+            grid = std::min(n_tiles, (unsigned)std::max(1, sdfa_cu_count() - a.reserve_cus));
+            const hipError_t e = hipMemsetAsync(a.tile_counter, 0, sizeof(int), s);
             if (e != hipSuccess) return e;
         }
-        if (pl == 3) {
-            if (persist) hipLaunchKernelGGL((freq_lstm_bf16p_v3_kernel<SHARED, true, 3>), dim3(grid), dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((freq_lstm_bf16p_v3_kernel<SHARED, false, 3>), dim3(grid), dim3(256), lds, s, a);
-        } else {
-            if (persist) hipLaunchKernelGGL((freq_lstm_bf16p_v3_kernel<SHARED, true, 2>), dim3(grid), dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((freq_lstm_bf16p_v3_kernel<SHARED, false, 2>), dim3(grid), dim3(256), lds, s, a);
-        }
-        return hipGetLastError();
+        return launch_lds(kernel, grid, 256, lds, s, a);
     }
     if (a.terms == 6) {                      // shape 3: the two-per-CU form (shares a CU with other streams' kernels)
         const size_t lds = (size_t)(3 * 16 * 64 + 3 * 8 * 64) * sizeof(bf16x8) + 512 * sizeof(float);      // 74 KiB: two workgroups per CU
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(freq_lstm_bf16x6_kernel<SHARED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((freq_lstm_bf16x6_kernel<SHARED>), dim3((unsigned)(a.Mc / 64 * 2)), dim3(256), lds, s, a);
-        return hipGetLastError();
+        return launch_lds(freq_lstm_bf16x6_kernel<SHARED>, n_tiles, 256, lds, s, a);
     }
-    if (a.terms == 1)
-        hipLaunchKernelGGL((freq_lstm_bf16_kernel<SHARED, 1>), dim3((unsigned)(a.Mc / 64 * 2)), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((freq_lstm_bf16_kernel<SHARED, 3>), dim3((unsigned)(a.Mc / 64 * 2)), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_lds(a.terms == 1 ? freq_lstm_bf16_kernel<SHARED, 1> : freq_lstm_bf16_kernel<SHARED, 3>, n_tiles, 256, 0, s, a);
 }
 
 hipError_t sdfa_launch_freq_lstm(const FreqLstmArgs &a, hipStream_t s) {
@@ -2096,39 +1892,23 @@ hipError_t sdfa_launch_freq_lstm(const FreqLstmArgs &a, hipStream_t s) {
 template <int NT, bool MAP>
 static hipError_t launch_time(const TimeLstmArgs &a, hipStream_t s) {
     const size_t lds = 2 * 64 * 32 * NT * sizeof(float4);   // 128 KiB (NT 2) / 64 KiB (NT 1)
-    {   // per launch: cheap, and correct for every device / thread the library is used from
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(time_lstm_kernel<NT, MAP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((time_lstm_kernel<NT, MAP>), dim3((unsigned)(a.Nc / (32 * NT) * 2)), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds(time_lstm_kernel<NT, MAP>, (unsigned)(a.Nc / (32 * NT) * 2), 512, lds, s, a);
 }
 
 template <int NT, int TERMS>
 static hipError_t launch_time_bf16(const TimeLstmArgs &a, hipStream_t s) {
     const size_t lds = (size_t)2 * (TERMS == 6 ? 3 : (TERMS > 1 ? 2 : 1)) * 32 * 32 * NT * sizeof(bf16x8)    // 128 KiB (NT 2, split) ... 32 KiB; 96 KiB (NT 1, six-product)
                        + (NT == 2 && TERMS != 6 ? 4 * 512 * sizeof(float4) : 0);                                  // + 32 KiB: column tile 1's cell state (160 KiB in all for NT 2, split)
-    {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(time_lstm_bf16_kernel<NT, TERMS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((time_lstm_bf16_kernel<NT, TERMS>), dim3((unsigned)(a.Nc / (32 * NT) * 2)), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds(time_lstm_bf16_kernel<NT, TERMS>, (unsigned)(a.Nc / (32 * NT) * 2), 512, lds, s, a);
 }
 
-extern thread_local int g_sdfa_time_lstm_handoff;   // api.cpp ("time_lstm_handoff"): bit 0 = plain stores + agent release, bit 1 = agent acquire + plain loads; bit 2 (tests) = part 1 never publishes
-extern thread_local int g_sdfa_time_lstm_timeout_us; // api.cpp ("time_lstm_timeout_us"): bound of one wait for a partner workgroup
+extern thread_local int g_sdfa_time_lstm_handoff;   // api_core.cpp ("time_lstm_handoff"): bit 0 = plain stores + agent release, bit 1 = agent acquire + plain loads; bit 2 (tests) = part 1 never publishes
+extern thread_local int g_sdfa_time_lstm_timeout_us; // api_core.cpp ("time_lstm_timeout_us"): bound of one wait for a partner workgroup
 
 // Behind every launch of a cooperating-workgroup kernel: the repair pass (exits at once unless that launch timed out).
 template <bool MAP>
 static hipError_t launch_time_repair(const TimeLstmArgs &a, hipStream_t s) {
-    const size_t lds = 2 * 64 * 32 * sizeof(float4);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(time_lstm_repair_kernel<MAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(time_lstm_repair_kernel<MAP>, dim3((unsigned)(a.Nc / 32 * 2)), dim3(512), lds, s, a, a.flags);
-    return hipGetLastError();
+    return launch_lds(time_lstm_repair_kernel<MAP>, (unsigned)(a.Nc / 32 * 2), 512, 2 * 64 * 32 * sizeof(float4), s, a, a.flags);
 }
 
 static SplitCtl split_ctl(const TimeLstmArgs &a) {
@@ -2142,32 +1922,26 @@ static SplitCtl split_ctl(const TimeLstmArgs &a) {
 template <int G, bool MAP>
 static hipError_t launch_time_split(const TimeLstmArgs &a, hipStream_t s) {
     const size_t lds = 96 * 1024;      // 64 KiB used; 96 KiB requested so that two workgroups never share a CU (see the kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(time_lstm_split_kernel<G, MAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)(a.Nc / 32 * 2 * G);
     // this launch's time-out word + flag words (one per workgroup), zeroed every launch: a block of its own, a multiple of 16 bytes
-    e = hipMemsetAsync(a.flags, 0, ((size_t)grid + 4) * sizeof(unsigned), s);
+    hipError_t e = hipMemsetAsync(a.flags, 0, ((size_t)grid + 4) * sizeof(unsigned), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_lstm_split_kernel<G, MAP>), dim3(grid), dim3(512 / G), lds, s, a, split_ctl(a));
-    e = hipGetLastError();
+    e = launch_lds(time_lstm_split_kernel<G, MAP>, grid, 512 / G, lds, s, a, split_ctl(a));
     return e != hipSuccess ? e : launch_time_repair<MAP>(a, s);
 }
 
 template <bool MAP>
 static hipError_t launch_time_split16(const TimeLstmArgs &a, hipStream_t s) {
     const size_t lds = 96 * 1024;      // 32 KiB used; 96 KiB requested: one workgroup per CU (hand-off form, see time_lstm_split_kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(time_lstm_split16_kernel<MAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)(a.Nc / 16 * 2 * 2);
-    e = hipMemsetAsync(a.flags, 0, ((size_t)grid + 4) * sizeof(unsigned), s);
+    hipError_t e = hipMemsetAsync(a.flags, 0, ((size_t)grid + 4) * sizeof(unsigned), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(time_lstm_split16_kernel<MAP>, dim3(grid), dim3(256), lds, s, a, split_ctl(a));
-    e = hipGetLastError();
+    e = launch_lds(time_lstm_split16_kernel<MAP>, grid, 256, lds, s, a, split_ctl(a));
     return e != hipSuccess ? e : launch_time_repair<MAP>(a, s);
 }
 
-extern thread_local int g_sdfa_time_lstm_split;   // api.cpp ("time_lstm_split" option): 0 = by size, 1 = never
-extern thread_local int g_sdfa_time_lstm_fuse_x;  // api.cpp ("time_lstm_fuse_x" option): 0 = by rule, 1 = never, 2 / 3 = always, 32- / 64-frame tiles
+extern thread_local int g_sdfa_time_lstm_split;   // api_core.cpp ("time_lstm_split" option): 0 = by size, 1 = never
+extern thread_local int g_sdfa_time_lstm_fuse_x;  // api_core.cpp ("time_lstm_fuse_x" option): 0 = by rule, 1 = never, 2 / 3 = always, 32- / 64-frame tiles
 
 // 64-frame tiles while they fill the 256 CUs (one 8-wave workgroup per CU); otherwise 32-frame tiles
 static bool time_big(const TimeLstmArgs &a) { return (a.Nc / 64) * 2 >= 256; }
@@ -2179,9 +1953,7 @@ static int time_split_form(const TimeLstmArgs &a) {
     // small batches: the gate rows of a tile split over G cooperating workgroups (time_lstm_split_kernel).  They exchange h
     // every step, so all of them should be resident at once: only while the grid fits the CUs this model may use (one
     // workgroup per CU; sdfa_model_set_reserved_cus leaves some to other streams)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    cus -= a.reserve_cus;
+    const int cus = sdfa_cu_count() - a.reserve_cus;
     const int64_t wg1 = a.Nc / 32 * 2;                       // workgroups of time_lstm_kernel<1>
     const bool range_ok = (int64_t)64 * a.Mc * 16 + (int64_t)a.Mc * 16 < 0x7fffffff && a.Nc % 128 == 0 && a.flag_words >= wg1 * 2 + 4;   // buffer offsets; 8-block groups
     // 16-frame tiles (time_lstm_split16_kernel) while even their grid -- twice the workgroups -- fits the CUs; option 16 / 32 force one
@@ -2196,10 +1968,7 @@ template <int NT>
 static hipError_t launch_time_fused(const TimeLstmArgs &a, hipStream_t s) {
     if (a.Nc % (32 * NT)) return hipErrorInvalidValue;
     const size_t lds = (2 * 64 + 2 * 16) * 32 * NT * sizeof(float4);   // 160 KiB (NT 2) / 80 KiB (NT 1)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(time_lstm_fused_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_lstm_fused_kernel<NT>), dim3((unsigned)(a.Nc / (32 * NT) * 2)), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds(time_lstm_fused_kernel<NT>, (unsigned)(a.Nc / (32 * NT) * 2), 512, lds, s, a);
 }
 
 template <bool MAP>
@@ -2214,7 +1983,7 @@ static hipError_t launch_time_any(const TimeLstmArgs &a, hipStream_t s) {
     if (split < 0) return hipErrorInvalidValue;
     if (split == 2) return launch_time_split<2, MAP>(a, s);
     if (a.terms) {
-        if (!a.Wb || MAP) return hipErrorInvalidValue;      // the bf16 recurrences read un-shared input projections (api.cpp expands first)
+        if (!a.Wb || MAP) return hipErrorInvalidValue;      // the bf16 recurrences read un-shared input projections (api_forward.cpp expands first)
         if (a.terms == 6) return launch_time_bf16<1, 6>(a, s);      // three planes of h: 32-frame tiles only (96 KiB of LDS)
         if (a.terms == 1) return big ? launch_time_bf16<2, 1>(a, s) : launch_time_bf16<1, 1>(a, s);
         return big ? launch_time_bf16<2, 3>(a, s) : launch_time_bf16<1, 3>(a, s);
