@@ -2,7 +2,13 @@
 
 The vertex stage and the raster / depth stage are written with explicit element-wise float32 operations in the kernel's
 order (no BLAS, no fused multiply-add), so snapped screen positions and the visibility buffer are reproduced bit for
-bit; the shading stage follows the same formulas (the GPU tests allow +-1 per channel there)."""
+bit; the shading stage follows the same formulas (the GPU tests allow +-1 per channel there).
+
+A restatement agrees with the kernel on a wrong rule, so this file is itself held to an independent float64 ray caster
+(tests/render_ref64.py: no edge functions, no snapping, no fp32) by tests/test_render_ref64_cpu.py: visibility of every sample
+outside 1/256 pixel of a projected edge, colour within a per-pixel bound formed from the reference alone, and seven patched
+copies of this source (winding, y flip, aspect, depth order, affine interpolation, channel order, normals mode) that the
+comparison must reject."""
 import math
 
 import numpy as np
