@@ -2,7 +2,8 @@
  * reference's FreqLstm (speech_anime/layers/freq_lstm.py, layer 6 of the audio encoder) -- a bidirectional
  * torch.nn.LSTM(64, 128, bias=True) that runs along the 32 frequency bins of every column, and _proj, a Linear(8192, 256) with bias --
  * as a training forward that keeps what the backward needs, back-propagation through the 32 steps down to dC, and one step of
- * torch.optim.Adam (amsgrad off, weight decay 0).  The stage that consumes the dX of an sdfa_lstmtrain handle of width 256.
+ * torch.optim.Adam (amsgrad off, weight decay 0).  The stage that consumes the dX of an sdfa_lstmtrain handle of width 256; its dC
+ * is what an sdfa_convtrain handle (sdfa_convtrain.h) reads.
  * DESIGN.md section 21.
  *
  * Conventions are those of sdfa_hip.h and sdfa_lstmtrain.h: every call returns >= 0 on success and a negative SDFA_E* code on

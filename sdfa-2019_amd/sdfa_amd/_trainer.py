@@ -1,5 +1,5 @@
-"""What the GPU trainers (sdfa_amd.headtrain, attntrain, lstmtrain, freqtrain) share on the host: a handle of libsdfa_hip.so that owns
-parameters, gradients and the Adam state on the device (csrc/trainstate.h), read and written under the reference's tensor names,
+"""What the GPU trainers (sdfa_amd.headtrain, attntrain, lstmtrain, freqtrain, convtrain) share on the host: a handle of
+libsdfa_hip.so that owns parameters, gradients and the Adam state on the device (csrc/trainstate.h), read and written under the reference's tensor names,
 and the weak registry through which a custom op of sdfa_amd.ops finds its trainer.  A subclass names its symbol prefix and its
 tensors and supplies forward and backward; DESIGN.md section 20."""
 import ctypes as C
@@ -27,18 +27,20 @@ def _f32(v):
 
 class Trainer:
     """A training handle `sdfa_<ABI>_*`: created with `create_args`, given the tensors of `shapes` ({name without "_model.": shape})
-    that `state_dict` has, and finalised on `device`.  step() is one torch.optim.Adam step;  grads() / parameters() read back under
-    the reference's names;  state_dict() / load_state_dict() carry parameters, both moments and the step count, so a fit can resume."""
+    and of `constants` (required, never stepped) that `state_dict` has, and finalised on `device`.  step() is one torch.optim.Adam
+    step;  grads() / parameters() read back under the reference's names;  state_dict() / load_state_dict() carry parameters, both
+    moments and the step count, so a fit can resume."""
 
     ABI = None          # "headtrain": the symbols are sdfa_headtrain_create, ...
 
     def _fn(self, name):
         return getattr(lib, f"sdfa_{self.ABI}_{name}")
 
-    def __init__(self, state_dict, shapes, create_args=(), lr=1e-4, betas=(0.9, 0.999), eps=1e-8, device=None):
+    def __init__(self, state_dict, shapes, create_args=(), lr=1e-4, betas=(0.9, 0.999), eps=1e-8, device=None, constants=None):
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.shapes = shapes
+        self.constants = dict(constants or {})               # tensors the handle requires and never steps: {name: shape}
         self._h = None
         h = self._fn("create")(*create_args)
         if not h:
@@ -46,7 +48,7 @@ class Trainer:
         self._h = C.c_void_p(h)
         self._finalizer = weakref.finalize(self, self._fn("destroy"), self._h)
         given = {_strip(k): v for k, v in state_dict.items()}
-        for name in self.shapes:
+        for name in (*self.shapes, *self.constants):
             if name not in given:
                 continue                                     # finalize names the first missing tensor
             a = _f32(given[name])

@@ -23,6 +23,8 @@ host through PyTorch-ROCm custom ops"; SURVEY.md section 8(b) names them).
     torch.ops.sdfa.encoder_conv(audio_feat, model)                                        -> C f32[N,64,32,64], the conv stack's output as the frequency LSTM reads it (no frequency LSTM)
     torch.ops.sdfa.freq_train(C, trainer_key)                                             -> X0 f32[N,64,256] of a FreqTrainer's frequency LSTM and projection;
                                                                                              backward leaves their gradients in the trainer, returns dC (or None)
+    torch.ops.sdfa.conv_train(audio_feat, trainer_key)                                    -> C f32[N,64,32,64] of a ConvTrainer's conv stack;
+                                                                                             backward leaves its gradients in the trainer, returns None
 
 Thin by design: each op is the matching `Engine` method (ctypes call into libsdfa_hip.so on the current stream), registered
 with the dispatcher through `torch.library.custom_op` and given a fake-tensor shape function, so the ops compose with
@@ -386,7 +388,8 @@ def freq_train(C: Tensor, trainer_key: str) -> Tensor:
     """sdfa_freqtrain_forward of the FreqTrainer registered as `trainer_key` (sdfa_amd.freqtrain.register_trainer): the training
     forward of the frequency LSTM and its projection, C f32[N,64,32,64] -> X0 f32[N,64,256].  The parameters live in the trainer,
     not in the graph: the backward needs C to require grad, runs sdfa_freqtrain_backward, OVERWRITES the trainer's parameter
-    gradients and returns dC -- or None (a null d_dC) unless the trainer has want_dC = True: the conv stack is frozen."""
+    gradients and returns dC -- or None (a null d_dC) unless the trainer has want_dC = True, which a conv-stack trainer below it
+    asks for."""
     from .freqtrain import trainer_of
     return trainer_of(trainer_key).forward(C.contiguous())
 
@@ -407,6 +410,36 @@ def _freq_train_backward(ctx, grad_X0):
 
 
 freq_train.register_autograd(_freq_train_backward, setup_context=_freq_train_setup)
+
+
+# --------------------------------------------------------------------------------------------------- conv stack training
+@custom_op("sdfa::conv_train", mutates_args=(), device_types="cuda")
+def conv_train(audio_feat: Tensor, trainer_key: str) -> Tensor:
+    """sdfa_convtrain_forward of the ConvTrainer registered as `trainer_key` (sdfa_amd.convtrain.register_trainer): the training
+    forward of the conv stack, audio_feat f32[N,64,128,3] -> C f32[N,64,32,64].  The parameters live in the trainer, not in the
+    graph: the backward needs audio_feat to require grad (pass audio_feat.detach().requires_grad_(True)), runs
+    sdfa_convtrain_backward, OVERWRITES the trainer's parameter gradients and returns None: the features are data."""
+    from .convtrain import trainer_of
+    return trainer_of(trainer_key).forward(audio_feat.contiguous())
+
+
+@conv_train.register_fake
+def _(audio_feat, trainer_key):
+    return audio_feat.new_empty((audio_feat.shape[0], 64, 32, 64))
+
+
+def _conv_train_setup(ctx, inputs, output):
+    ctx.trainer_key = inputs[1]
+    ctx.save_for_backward(inputs[0])
+
+
+def _conv_train_backward(ctx, grad_C):
+    from .convtrain import trainer_of
+    trainer_of(ctx.trainer_key).backward(ctx.saved_tensors[0], grad_C.contiguous())
+    return None, None
+
+
+conv_train.register_autograd(_conv_train_backward, setup_context=_conv_train_setup)
 
 
 class TraceableSpeechDrivenAnimation(torch.nn.Module):

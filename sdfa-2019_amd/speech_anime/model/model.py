@@ -218,7 +218,8 @@ class SaberSpeechDrivenAnimation:
             raise NotImplementedError(f"head training: optim.args {sorted(unknown)} are not built")
         return dict(lr=float(args.get("lr", 1e-4)), betas=tuple(args.get("betas", (0.9, 0.999))), eps=float(args.get("eps", 1e-8)))
 
-    def enable_head_training(self, state_dict, attention=False, bilstm_top=False, bilstm_dropout=0.0, bilstm_bottom=False, freq_lstm=False):
+    def enable_head_training(self, state_dict, attention=False, bilstm_top=False, bilstm_dropout=0.0, bilstm_bottom=False, freq_lstm=False,
+                             conv_stack=False):
         """Make the regressor head of `state_dict` (the one given to load_state_dict: weight_g / weight_v / bias under the
         reference's names) trainable on the device, with the encoder frozen: a sdfa_amd.headtrain.HeadTrainer with the
         reference's optimiser, and the PCA bases for get_loss.  The finalised inference engine stays read-only; commit_head()
@@ -241,8 +242,16 @@ class SaberSpeechDrivenAnimation:
 
         freq_lstm=True (with bilstm_bottom=True) also trains the frequency LSTM and its projection (layer 6 of the audio encoder;
         DESIGN.md section 21) through a sdfa_amd.freqtrain.FreqTrainer: the frozen stack ends at the conv stack
-        (torch.ops.sdfa.encoder_conv), the bottom layer forms dX0, and everything above the conv stack trains."""
+        (torch.ops.sdfa.encoder_conv), the bottom layer forms dX0, and everything above the conv stack trains.
+
+        conv_stack=True (with freq_lstm=True) also trains the conv stack (layers 1, 3 and 5 of the audio encoder; DESIGN.md section
+        22) through a sdfa_amd.convtrain.ConvTrainer: the frequency LSTM forms dC, every parameter the reference's optimiser holds
+        trains, and the frozen engine no longer runs inside a training step.  BatchNorm keeps its running statistics (the
+        inference form, as bilstm_dropout=0.0 is): the reference's train() mode, batch statistics and moving running ones, is
+        not built."""
         from sdfa_amd.headtrain import HeadTrainer, register_trainer
+        if conv_stack and not freq_lstm:
+            raise NotImplementedError("head training: conv_stack=True needs freq_lstm=True: the conv stack is trained through the frequency LSTM's dC")
         if freq_lstm and not bilstm_bottom:
             raise NotImplementedError("head training: freq_lstm=True needs bilstm_bottom=True: the frequency LSTM is trained through the bottom layer's dX")
         if bilstm_bottom and not bilstm_top:
@@ -263,11 +272,14 @@ class SaberSpeechDrivenAnimation:
         self._lstm_trainer = self._lstm_trainer_key = None
         self._lstm0_trainer = self._lstm0_trainer_key = None
         self._freq_trainer = self._freq_trainer_key = None
+        self._conv_trainer = self._conv_trainer_key = None
         self._bilstm_dropout = float(bilstm_dropout)
         self._train_flags = dict(attention=bool(attention), bilstm_top=bool(bilstm_top), bilstm_bottom=bool(bilstm_bottom),
                                  bilstm_dropout=float(bilstm_dropout))
-        if freq_lstm:
-            self._train_flags["freq_lstm"] = True      # the key exists only when set: a state taken without it has the flags it always had
+        when_set = dict(freq_lstm=freq_lstm, conv_stack=conv_stack)
+        assert set(when_set) == set(self._FLAGS_WHEN_SET)
+        # the key exists only when set: a state taken without it has the flags it always had
+        self._train_flags.update({name: True for name, on in when_set.items() if on})
         if attention:
             from sdfa_amd import attntrain
             # dH is consumed by the BiLSTM layer's backward, and by nothing without it
@@ -284,8 +296,13 @@ class SaberSpeechDrivenAnimation:
             self._lstm0_trainer_key = lstmtrain.register_trainer(self._lstm0_trainer)
         if freq_lstm:
             from sdfa_amd import freqtrain
-            self._freq_trainer = freqtrain.FreqTrainer(state_dict, device=self._model._engine.device, want_dC=False, **optim)   # the conv stack is frozen
+            # dC is consumed by the conv stack's backward, and by nothing while it is frozen
+            self._freq_trainer = freqtrain.FreqTrainer(state_dict, device=self._model._engine.device, want_dC=bool(conv_stack), **optim)
             self._freq_trainer_key = freqtrain.register_trainer(self._freq_trainer)
+        if conv_stack:
+            from sdfa_amd import convtrain
+            self._conv_trainer = convtrain.ConvTrainer(state_dict, device=self._model._engine.device, **optim)
+            self._conv_trainer_key = convtrain.register_trainer(self._conv_trainer)
         return self
 
     def _bilstm_keep_mask(self, X1):
@@ -313,7 +330,8 @@ class SaberSpeechDrivenAnimation:
         is set, and layer 1 of the BiLSTM runs through torch.ops.sdfa.lstm_train in front of the attention layer.  With
         bilstm_bottom=True the frozen stack ends at the BiLSTM's input (torch.ops.sdfa.encoder_x0) and both layers run through
         torch.ops.sdfa.lstm_train, the keep mask between them inside the graph.  With freq_lstm=True the frozen stack ends at the
-        conv stack (torch.ops.sdfa.encoder_conv) and the frequency LSTM runs through torch.ops.sdfa.freq_train in front of them."""
+        conv stack (torch.ops.sdfa.encoder_conv) and the frequency LSTM runs through torch.ops.sdfa.freq_train in front of them.
+        With conv_stack=True the conv stack runs through torch.ops.sdfa.conv_train and no encoder_* operator is called."""
         tr = self._trainer()
         self.train()
         if getattr(self, "_lstm0_trainer", None) is not None:
@@ -321,10 +339,15 @@ class SaberSpeechDrivenAnimation:
             # product rule: nn.LSTM's inter-layer dropout with both layers trained) into layer 0's; the frequency LSTM and
             # everything below are frozen, so no dX0 is formed
             if getattr(self, "_freq_trainer", None) is not None:
-                # the frequency LSTM as well: layer 0's dX0 flows into its backward; the conv stack is frozen, so no dC is formed
-                with torch.no_grad():
-                    Cx = torch.ops.sdfa.encoder_conv(batch["audio_feat"].contiguous(), self._model._key)
-                Cx = Cx.detach().requires_grad_(True)
+                # the frequency LSTM as well: layer 0's dX0 flows into its backward; while the conv stack is frozen no dC is formed
+                if getattr(self, "_conv_trainer", None) is not None:
+                    # the conv stack as well: the frequency LSTM's dC flows into its backward; audio_feat is data
+                    feat = batch["audio_feat"].contiguous().detach().requires_grad_(True)
+                    Cx = torch.ops.sdfa.conv_train(feat, self._conv_trainer_key)
+                else:
+                    with torch.no_grad():
+                        Cx = torch.ops.sdfa.encoder_conv(batch["audio_feat"].contiguous(), self._model._key)
+                    Cx = Cx.detach().requires_grad_(True)
                 X0 = torch.ops.sdfa.freq_train(Cx, self._freq_trainer_key)
             else:
                 with torch.no_grad():
@@ -380,6 +403,9 @@ class SaberSpeechDrivenAnimation:
         fq = getattr(self, "_freq_trainer", None)
         if fq is not None and fq.step_count != tr.step_count:
             raise RuntimeError(f"head trainer at step {tr.step_count}, frequency-LSTM trainer at step {fq.step_count}: they step together")
+        cv = getattr(self, "_conv_trainer", None)
+        if cv is not None and cv.step_count != tr.step_count:
+            raise RuntimeError(f"head trainer at step {tr.step_count}, conv-stack trainer at step {cv.step_count}: they step together")
         tr.step()
         if at is not None:
             at.step()
@@ -389,6 +415,8 @@ class SaberSpeechDrivenAnimation:
             l0.step()
         if fq is not None:
             fq.step()
+        if cv is not None:
+            cv.step()
 
     def fit_head(self, trainset, steps, rng, batch_size=50, noise="device", fixed_batch=None):
         """`steps` steps of the reference's loop (trainer.py:266-320: train_step, the summed losses' backward, optim.step) over
@@ -412,7 +440,9 @@ class SaberSpeechDrivenAnimation:
         attention training enabled the tuned attention tensors ("_model._audio_encoder._layers.10. ..."), with bilstm_top the
         four tuned layer-1 tensors of the BiLSTM ("_model._audio_encoder._layers.9.weight_ih_l1 ..."), with bilstm_bottom the
         four layer-0 tensors ("... weight_ih_l0", "weight_hh_l0" and their "_reverse" twins), with freq_lstm the ten tensors of
-        the frequency LSTM and its projection ("_model._audio_encoder._layers.6._lstm. ...", "..._proj.weight | bias")."""
+        the frequency LSTM and its projection ("_model._audio_encoder._layers.6._lstm. ...", "..._proj.weight | bias"), with
+        conv_stack the 15 tensors of the conv stack ("_model._audio_encoder._layers.1 | 3 | 5.weight_g | weight_v | bias |
+        _ext_post_bn.weight | _ext_post_bn.bias"; the running statistics are not trained)."""
         tuned = self._trainer().head_state_dict()
         if getattr(self, "_attn_trainer", None) is not None:
             tuned.update(self._attn_trainer.attn_state_dict())
@@ -422,15 +452,18 @@ class SaberSpeechDrivenAnimation:
             tuned.update(self._lstm0_trainer.lstm_state_dict())
         if getattr(self, "_freq_trainer", None) is not None:
             tuned.update(self._freq_trainer.freq_state_dict())
+        if getattr(self, "_conv_trainer", None) is not None:
+            tuned.update(self._conv_trainer.conv_state_dict())
         return tuned
 
     # ---- save, stop, resume: what a training loop around train_step has to carry ----
     _TRAINER_SLOTS = (("head", "_head_trainer"), ("attention", "_attn_trainer"), ("bilstm_top", "_lstm_trainer"), ("bilstm_bottom", "_lstm0_trainer"),
-                      ("freq_lstm", "_freq_trainer"))
+                      ("freq_lstm", "_freq_trainer"), ("conv_stack", "_conv_trainer"))
+    _FLAGS_WHEN_SET = ("freq_lstm", "conv_stack")       # flags whose key exists only when true
 
     def training_state_dict(self):
         """Everything a fit needs to continue bit for bit: every enabled trainer's state_dict() (parameters, both Adam moments,
-        the step count, the optimiser arguments) under "head", "attention", "bilstm_top", "bilstm_bottom", "freq_lstm"; the
+        the step count, the optimiser arguments) under "head", "attention", "bilstm_top", "bilstm_bottom", "freq_lstm", "conv_stack"; the
         DynamicLossScalers' state by the reference's names; the dropout generator's state (None while nothing has been drawn);
         and the flags enable_head_training was called with.  Host data only, so torch.save takes it."""
         self._trainer()
@@ -445,9 +478,11 @@ class SaberSpeechDrivenAnimation:
         by name, before anything is changed."""
         self._trainer()
         theirs, mine = dict(state["flags"]), self._train_flags
-        differ = [f"{k}={theirs.get(k)!r} (this model: {k}={mine[k]!r})" for k in mine if k != "freq_lstm" and theirs.get(k) != mine[k]]
-        if bool(theirs.get("freq_lstm", False)) != bool(mine.get("freq_lstm", False)):      # a key that exists only when set
-            differ.append(f"freq_lstm={bool(theirs.get('freq_lstm', False))!r} (this model: freq_lstm={bool(mine.get('freq_lstm', False))!r})")
+        differ = [f"{k}={theirs.get(k)!r} (this model: {k}={mine[k]!r})" for k in mine if k not in self._FLAGS_WHEN_SET and theirs.get(k) != mine[k]]
+        for k in self._FLAGS_WHEN_SET:                  # a key that exists only when set: absent is False, either way round
+            a, b = bool(theirs.get(k, False)), bool(mine.get(k, False))
+            if a != b:
+                differ.append(f"{k}={a!r} (this model: {k}={b!r})")
         if differ or set(theirs) != set(mine):
             raise ValueError("training state: taken with " + ", ".join(differ or sorted(set(theirs) ^ set(mine))) +
                              ": enable_head_training must be called with the flags the state was taken with")

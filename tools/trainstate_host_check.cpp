@@ -1,14 +1,16 @@
 // Host-only check of the training handles' shared core (sdfa-2019_amd/csrc/trainstate.h), which frees and copies: without a device,
-// for each of sdfa_headtrain, sdfa_attntrain, sdfa_lstmtrain and sdfa_freqtrain: create, set_tensor (good name, bad name, short numel, null
+// for each of sdfa_headtrain, sdfa_attntrain, sdfa_lstmtrain, sdfa_freqtrain and sdfa_convtrain: create, set_tensor (good name, bad name, short numel, null
 // data), the finalize-with-a-missing-tensor refusal, the calls an unfinalised handle refuses, and destroy of the unfinalised handle.
 // Meant to run under AddressSanitizer and UBSan on the host side only, from sdfa-2019_amd/csrc:
 //
 //   hipcc -std=c++17 --offload-arch=gfx950 -g -O1 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
 //       -x hip ../../tools/trainstate_host_check.cpp api_core.cpp api_headtrain.cpp api_attntrain.cpp api_lstmtrain.cpp \
-//       api_freqtrain.cpp headtrain.hip attntrain.hip lstmtrain.hip freqtrain.hip -o trainstate_host_check && ./trainstate_host_check
+//       api_freqtrain.cpp api_convtrain.cpp headtrain.hip attntrain.hip lstmtrain.hip freqtrain.hip convtrain.hip \
+//       -o trainstate_host_check && ./trainstate_host_check
 //
 // It launches nothing; exit status 0 and "trainstate host check: ok" is a pass, a sanitizer report is a failure.
 #include "../include/sdfa_attntrain.h"
+#include "../include/sdfa_convtrain.h"
 #include "../include/sdfa_freqtrain.h"
 #include "../include/sdfa_headtrain.h"
 #include "../include/sdfa_hip.h"
@@ -110,6 +112,8 @@ int main() {
          {{"_audio_encoder._layers.9.weight_ih_l1", 1024 * 512}, {"_audio_encoder._layers.9.weight_ih_l1_reverse", 1024 * 512}, {"_audio_encoder._layers.9.weight_hh_l1_reverse", 1024 * 256}}},
         {"freqtrain", API(freqtrain, sdfa_freqtrain_create()),
          {{"_audio_encoder._layers.6._lstm.weight_ih_l0", 512 * 64}, {"_audio_encoder._layers.6._lstm.weight_ih_l0_reverse", 512 * 64}, {"_audio_encoder._layers.6._proj.bias", 256}}},
+        {"convtrain", API(convtrain, sdfa_convtrain_create()),
+         {{"_audio_encoder._layers.1.weight_g", 32}, {"_audio_encoder._layers.1.weight_v", 32 * 9}, {"_audio_encoder._layers.5._ext_post_bn.bias", 64}}},
     };
     for (const Api &a : apis) run(a);
     expect("headtrain_create(7)", sdfa_headtrain_create(7) ? 0 : -1, -1, "unknown head");
@@ -128,6 +132,29 @@ int main() {
         expect("freqtrain: workspace_bytes(MAX) > 2^34", sdfa_freqtrain_workspace_bytes(h, SDFA_FREQTRAIN_MAX_FRAMES) > ((int64_t)1 << 34), 1, nullptr);
         sdfa_freqtrain_destroy(h);                                      // before finalize
         expect("freqtrain: forward, null handle", sdfa_freqtrain_forward(nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr), SDFA_EINVAL, "null handle");
+    }
+    // the conv-stack handle's own calls: its constants, which lie outside the flat buffers, and the step's refusals
+    {
+        sdfa_convtrain *h = sdfa_convtrain_create();
+        std::vector<float> v((size_t)64 * 32 * 3, 0.5f), c32(32, 1.f), c64(64, 1.f);      // exactly numel floats each
+        const char *mean1 = "_audio_encoder._layers.1._ext_post_bn.running_mean", *var5 = "_audio_encoder._layers.5._ext_post_bn.running_var";
+        expect("convtrain: set_tensor, layer 3's weight_v", sdfa_convtrain_set_tensor(h, "_audio_encoder._layers.3.weight_v", v.data(), (int64_t)v.size()), SDFA_OK, nullptr);
+        expect("convtrain: set_tensor, a constant", sdfa_convtrain_set_tensor(h, mean1, c32.data(), 32), SDFA_OK, nullptr);
+        expect("convtrain: set_tensor, the last constant", sdfa_convtrain_set_tensor(h, var5, c64.data(), 64), SDFA_OK, nullptr);
+        expect("convtrain: set_tensor, a constant, short numel", sdfa_convtrain_set_tensor(h, var5, c64.data(), 63), SDFA_EINVAL, "elements");
+        expect("convtrain: set_tensor, the frequency LSTM's name", sdfa_convtrain_set_tensor(h, "_audio_encoder._layers.6._proj.bias", c64.data(), 256), SDFA_EINVAL,
+               "the conv stack has no tensor");
+        expect("convtrain: set_state on a constant", sdfa_convtrain_set_state(h, mean1, 0, c32.data(), 32), SDFA_EINVAL, "is a constant");
+        expect("convtrain: set_grad on a constant", sdfa_convtrain_set_grad(h, var5, c64.data(), 64), SDFA_EINVAL, "is a constant");
+        expect("convtrain: get_tensor of a constant, unfinalised", sdfa_convtrain_get_tensor(h, mean1, 0, c32.data(), 32), SDFA_ESTATE, "not finalised");
+        expect("convtrain: finalize, a trainable tensor missing", sdfa_convtrain_finalize(h, nullptr), SDFA_ESTATE, "_layers.1.weight_g");
+        expect("convtrain: forward, unfinalised", sdfa_convtrain_forward(h, nullptr, 1, nullptr, nullptr, 0, nullptr), SDFA_ESTATE, "not finalised");
+        expect("convtrain: backward, unfinalised", sdfa_convtrain_backward(h, nullptr, nullptr, 1, nullptr, 0, nullptr), SDFA_ESTATE, "not finalised");
+        expect("convtrain: workspace_bytes(0)", sdfa_convtrain_workspace_bytes(h, 0), SDFA_EINVAL, "frames outside");
+        expect("convtrain: workspace_bytes(MAX + 1)", sdfa_convtrain_workspace_bytes(h, SDFA_CONVTRAIN_MAX_FRAMES + 1), SDFA_EINVAL, "frames outside");
+        expect("convtrain: workspace_bytes(MAX) > 2^33", sdfa_convtrain_workspace_bytes(h, SDFA_CONVTRAIN_MAX_FRAMES) > ((int64_t)1 << 33), 1, nullptr);
+        sdfa_convtrain_destroy(h);                                      // before finalize
+        expect("convtrain: forward, null handle", sdfa_convtrain_forward(nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr), SDFA_EINVAL, "null handle");
     }
     printf(failures ? "trainstate host check: %d UNEXPECTED\n" : "trainstate host check: ok\n", failures);
     return failures ? 1 : 0;
